@@ -17,7 +17,15 @@ walkers per GPU, fixed-step RK4, t = linspace(0, 3, 1000), y0 = demo data
 observations = demo data (H = S+I1+I2, V).  Walkers shard across ranks by contiguous
 global id with no data-path collective ("scaling": "weak").
 
-Legs after the headline (all in the same JSON line):
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs: set-up,
+warm-up, the K timed steps, the output dump if ``--dump-outputs DIR`` is given, and the JSON
+line.  ``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/<name>.npy``
+(see ``dump_outputs``); the inputs are seeded, so two builds can be compared output for
+output.  Everything below — the CPU baselines, the PMC child passes, the per-dispatch and
+write-ceiling passes, the MCMC leg and the other configs — runs only with ``--full``; the
+``--no-*`` options then leave single legs out as before.
+
+Legs after the headline, with ``--full`` (all in the same JSON line):
 * ``mcmc``  — device Metropolis–Hastings (RK4, Philox) over the rank's walkers; its FP64
   roofline counts the kernel's fp64 operations with rocprofv3 PMC
   (SQ_INSTS_VALU_{FMA,ADD,MUL}_F64) in a child pass of the same MH call.
@@ -65,6 +73,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CPU baselines, rocprofv3 PMC child passes, "
+                         "per-dispatch and write-ceiling passes, the MCMC leg, C4 and the other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--warmup-ms", type=float, default=60.0,
                     help="continue the untimed warm-up until this much wall time has passed")
     ap.add_argument("--walkers", type=int, default=65536, help="walkers per GPU")
@@ -503,6 +516,36 @@ def write_ceiling(buf, stream, launches=20, warm_ms=60.0):
             "ms": ms, "GB/s": nbytes / (ms / 1e3) / 1e9}
 
 
+DUMP_TRAJ_BYTES = 48 << 20   # trajectory sample; with the per-walker vectors the dump stays under 64 MB
+DUMP_FULL_WALKERS = 1 << 18  # per-walker vectors are written whole up to this many walkers
+
+
+def dump_outputs(path, out, seed=20261019):
+    """--dump-outputs: what the last timed ``integrate`` returned to its caller, as float64
+    ``<path>/<name>.npy``: ``chi``, ``ssres``, ``status`` [W] and ``traj`` [T][S][k], the
+    trajectories of k walkers — all W if they fit DUMP_TRAJ_BYTES, else a sorted sample drawn
+    without replacement by numpy RandomState(seed), the same for every run of the same shape;
+    ``walkers`` holds their indices.  Beyond DUMP_FULL_WALKERS walkers the per-walker vectors
+    hold the same sample.  With several ranks, rank 0 writes its shard.  Returns name -> shape."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    traj = out["traj"]
+    T, S, W = traj.shape
+    k = min(W, max(1, DUMP_TRAJ_BYTES // (T * S * 8)))
+    idx = np.sort(np.random.RandomState(seed).choice(W, k, replace=False)) if k < W else np.arange(W)
+    ti = torch.as_tensor(idx, device=traj.device)
+    arrays = {"traj": traj.index_select(2, ti), "walkers": torch.as_tensor(idx)}
+    for name in ("chi", "ssres", "status"):
+        arrays[name] = out[name] if W <= DUMP_FULL_WALKERS else out[name].index_select(0, ti)
+    shapes = {}
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.cpu().numpy(), dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 # ------------------------------------------------------------------ GPU legs
 class Ranks:
     """This rank's device and the collectives the timing needs (barrier, max)."""
@@ -928,26 +971,27 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     P = 5
 
-    # host-side problem set-up, then the CPU baseline and the PMC child passes (all
+    # host-side problem set-up, then (--full) the CPU baseline and the PMC child passes (all
     # before this process touches the GPU)
+    full = args.full and not args.mcmc_only
     m, y0h = build_problem(args.model, args.method, args.times)
     fp_host = m.fit_problem()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.mcmc_only:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, fp_host, y0h, args.cpu_seconds, P)
         if args.method == "rk4":
             cpu["rk4_c_openmp"] = cpu_rk4_c(fp_host, y0h, args.walkers, cpu["cores"])
         if args.model == "two_i" and not args.no_extra_configs:
             cpu["mcmc_32chains"] = cpu_mcmc_baseline(m)
     demo = None
-    if args.model == "two_i" and not args.no_extra_configs and world == 1:
+    if full and args.model == "two_i" and not args.no_extra_configs and world == 1:
         dm = demo_model()
         demo = {"model": dm, "starts": demo_fit_starts(dm)}
         if cpu is not None:
             cpu["mcmc_demo_fit_32chains"] = cpu_demo_fit_baseline(dm, demo["starts"])
-    traffic, traffic_note = None, "skipped (--no-pmc or N>1)"
+    traffic, traffic_note = None, "skipped (--no-pmc or N>1)" if full else "skipped (needs --full)"
     mh_flops, mh_flops_note = None, "skipped (--no-pmc, N>1 or no MCMC leg)"
-    if world == 1 and not args.no_pmc and not args.mcmc_only:
+    if full and world == 1 and not args.no_pmc:
         traffic, traffic_note = pmc_traffic(args)
         if args.mcmc_iters > 1 and args.model == "two_i":
             mh_flops, mh_flops_note = pmc_mh_flops(args)
@@ -1008,36 +1052,43 @@ def main():
     # average launch duration over the timed region: HIP events bracketing the K
     # back-to-back launches on the launch stream
     kern_avg_s = span[0].elapsed_time(span[1]) / args.steps / 1e3
-    # per-dispatch durations (event pair around each launch; the rocprofv3 view), in an
-    # untimed pass of the same launches after the timed region
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
-    for k in range(args.steps):
-        ev[k][0].record(stream)
-        step()
-        ev[k][1].record(stream)
-    torch.cuda.synchronize(dev)
-    kern_dispatch_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+    chi_ok = bool(torch.isfinite(out["chi"]).all().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out)
+    kern_dispatch_ms = ceiling = None
+    if full:
+        # per-dispatch durations (event pair around each launch; the rocprofv3 view), in an
+        # untimed pass of the same launches after the timed region
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(args.steps)]
+        for k in range(args.steps):
+            ev[k][0].record(stream)
+            step()
+            ev[k][1].record(stream)
+        torch.cuda.synchronize(dev)
+        kern_dispatch_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
     ran = eng.last_variant()
     tune = eng.tune_times() if kernel == "auto" else None
-    ceiling = write_ceiling(traj, stream)
+    if full:
+        ceiling = write_ceiling(traj, stream)
     wts = world * Wl * (T - 1) * args.steps  # walkers every rank actually ran
     value = wts / elapsed
     bytes_launch = Wl * (T - 1) * 8 * S + Wl * 8 * (S + P + 2)  # traj + y0/θ/chi/ssres
     achieved = bytes_launch / kern_avg_s / 1e9
-    chi_ok = bool(torch.isfinite(out["chi"]).all().item())
     del traj, out
     torch.cuda.empty_cache()
 
     mcmc = None
-    if args.mcmc_iters > 1:
+    if full and args.mcmc_iters > 1:
         mcmc = mcmc_leg(args, R, eng, theta, y0, Wl, T, S, P)
         if args.model == "two_i":
             mcmc["roofline"] = mcmc_roofline(mcmc, mh_flops, mh_flops_note, Wl, T, args.mcmc_iters)
 
     extra = {}
-    if not args.no_c4 and args.model == "two_i":
+    if full and not args.no_c4 and args.model == "two_i":
         extra["C4"] = c4_leg(args, R, T, P)
-    if world == 1 and not args.no_extra_configs:
+    if full and world == 1 and not args.no_extra_configs:
         extra.update(extra_configs(args, R, T, P))
         if demo is not None:
             extra["MCMC-demo-fit-32chains"] = demo_fit_leg(demo, cpu)
@@ -1066,12 +1117,16 @@ def main():
                          "traffic_note": traffic_note,
                          "kernel_ms": kern_avg_s * 1e3, "kernel_ms_note": "timed-region event span / steps",
                          "kernel_ms_per_dispatch": kern_dispatch_ms, "bytes_per_launch": bytes_launch,
-                         "box_write_ceiling": dict(ceiling, frac_of_ceiling=achieved / ceiling["GB/s"])},
+                         "box_write_ceiling": dict(ceiling, frac_of_ceiling=achieved / ceiling["GB/s"])
+                         if ceiling else None},
+            "full": full,
             "cpu_baseline": cpu,
             "mcmc": mcmc,
             "other_configs": extra or None,
             "chi_finite": chi_ok,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         R.dist.destroy_process_group()

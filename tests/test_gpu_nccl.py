@@ -217,7 +217,7 @@ def test_bench_multi_rank_rehearsal(n):
     env = dict(os.environ, ODELIB_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-                        "--warmup-ms", "5", "--no-extra-configs", "--no-pmc", "--mcmc-iters", "5", "--c4-steps", "2"],
+                        "--full", "--warmup-ms", "5", "--no-extra-configs", "--no-pmc", "--mcmc-iters", "5", "--c4-steps", "2"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -3,7 +3,7 @@
 # with the box's write ceiling beside each (GPU box):  bash tools/ab_xcd.sh <tag>
 tag=$1
 for x in runs ranges off runs; do
-  timeout -k 10 120 python -u bench.py --no-cpu-baseline --mcmc-iters 0 --no-extra-configs --no-c4 --no-pmc \
+  timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --mcmc-iters 0 --no-extra-configs --no-c4 --no-pmc \
     --steps 20 --xcd $x > gpurun_out/${tag}_xcd_$x.log 2>&1 || exit 1
   python - "$x" "gpurun_out/${tag}_xcd_$x.log" <<'PY'
 import json, sys

@@ -105,7 +105,7 @@ def main():
     # 1. kernel trace + stats (same command line as the bench run, minus the CPU leg)
     d = os.path.join(out, "trace")
     stdout = run(rocprof() + ["--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--",
-                  sys.executable, "bench.py", "--no-cpu-baseline", "--no-extra-configs", "--no-c4", "--no-pmc",
+                  sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-extra-configs", "--no-c4", "--no-pmc",
                   *bench_args],
                  args.timeout)
     bench_line = [l for l in stdout.splitlines() if l.startswith("{")]

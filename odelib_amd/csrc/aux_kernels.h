@@ -1,0 +1,17 @@
+// aux_kernels.h — the model-independent kernels of the C-ABI (inst_aux.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "numpy_rng.cuh"
+#include "ode_kernels.cuh"
+
+// deepest tree k_mh_resolve_wave holds in LDS (4 095 nodes)
+constexpr int kResolveLdsDepth = 12;
+
+__global__ void k_stiff_list(const int32_t* __restrict__ status, int64_t W, int32_t* __restrict__ list,
+                             int32_t* __restrict__ count);
+__global__ void __launch_bounds__(256) k_np_seed(const oe::NpState st, const uint32_t* seeds, int64_t W);
+__global__ void __launch_bounds__(oe::kNpChainsPerBlock) k_np_draws(const oe::NpDrawArgs d);
+__global__ void __launch_bounds__(256) k_philox_draws(const oe::DrawArgs d);
+__global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S);
+__global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S);

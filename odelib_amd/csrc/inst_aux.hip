@@ -1,0 +1,211 @@
+// inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
+// (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution.
+// Device code only, built and linked with the model units (inst_*.hip).
+#include "aux_kernels.h"
+
+using oe::ST_STIFF;
+
+// ids of the walkers an 'auto' pass marked ST_STIFF (any order: each is redone on its own)
+__global__ void k_stiff_list(const int32_t* __restrict__ status, int64_t W, int32_t* __restrict__ list,
+                             int32_t* __restrict__ count) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < W && (status[w] & ST_STIFF)) list[atomicAdd(count, 1)] = (int32_t)w;
+}
+
+// numpy legacy RandomState per chain: seeding and one chunk of draws (numpy_rng.cuh)
+__global__ void __launch_bounds__(256) k_np_seed(const oe::NpState st, const uint32_t* seeds, int64_t W) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < W) oe::np_seed_lane(st, w, seeds[w]);
+}
+__global__ void __launch_bounds__(oe::kNpChainsPerBlock) k_np_draws(const oe::NpDrawArgs d) {
+  oe::np_draw_block<oe::kNpChainsPerBlock>(d);
+}
+
+// MH proposal draws (philox mode), one lane per (walker, iteration) of the chunk: counter-
+// based, so every draw is independent of the others (a few chains no longer draw their
+// iterations one after another); see oe::philox_draw_iteration
+__global__ void __launch_bounds__(256) k_philox_draws(const oe::DrawArgs d) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n_it = d.it1 - d.it0;
+  if (g >= d.W * n_it) return;
+  const int64_t k = g / d.W;
+  oe::philox_draw_iteration(d, g - k * d.W, d.it0 + (int)k);
+}
+
+// k_mh_tree's resolution: one lane per chain walks its tree with k_mh's accept test and
+// bookkeeping, iteration by iteration, in the reference's arithmetic (Samplers.py:124-153)
+__global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S) {
+  using namespace oe;
+  constexpr int kMaxD = 16;  // oe_mh_run caps the depth
+  const MHArgs& ma = ta.m;
+  const int64_t W = ma.W;
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= W) return;
+  const int P = pb.P;
+  const int PS = P + 5;
+  const int D = ta.depth;
+  const uint32_t off = (uint32_t)w * 8u;
+  double* cur = ma.cur;
+  double chi = Row(cur, W).ld(off), rsq = Row(cur + W, W).ld(off), aic = Row(cur + 2 * W, W).ld(off);
+  double nacc = Row(cur + 3 * W, W).ld(off);
+  // 1. the decisions.  The only loads on the path's dependency chain are the node chis; the
+  //    next level's two candidates are loaded before each decision, the uniforms up front.
+  //    exp/log inline (the same ocml functions k_mh calls out of line: the same bits).
+  double uj[kMaxD], cj[kMaxD], rj[kMaxD], aj[kMaxD], nj[kMaxD];
+  int32_t keep[kMaxD];  // node holding the chain's parameters after iteration j (-1: the round's start)
+#pragma unroll
+  for (int j = 0; j < kMaxD; ++j)
+    if (j < D) uj[j] = Row(ma.u + (int64_t)(ma.it0 + j - ma.draw_it0) * W, W).ld(off);
+  uint32_t path = 0;
+  int32_t last = -1;
+  double chin = ta.node_chi[w];
+#pragma unroll
+  for (int j = 0; j < kMaxD; ++j) {
+    if (j >= D) continue;  // (continue, not break: the loop must unroll, the arrays stay in registers)
+    const int64_t n = (int64_t)(1u << j) - 1 + path;
+    double c0 = 0.0, c1 = 0.0;
+    if (j + 1 < D) {
+      const int64_t n0 = (int64_t)(2u << j) - 1 + path;
+      c0 = ta.node_chi[n0 * W + w];
+      c1 = ta.node_chi[(n0 + (int64_t)(1u << j)) * W + w];
+    }
+    const double lr = exp(chi - chin);
+    const double accp = exp(log(lr));
+    const bool acc = accp > uj[j];
+    if (acc) {
+      chi = chin;
+      rsq = 1.0 - ta.node_ss[n * W + w] / pb.sstot;
+      aic = -2.0 * (-chi) + 2.0 * (double)pb.pnum;
+      nacc += 1.0;
+      last = (int32_t)n;
+    }
+    cj[j] = chi;
+    rj[j] = rsq;
+    aj[j] = aic;
+    nj[j] = nacc;
+    keep[j] = last;
+    path |= (acc ? 1u : 0u) << j;
+    chin = acc ? c1 : c0;
+  }
+  // 2. the sample rows (parameters from the node the chain holds, or from θ, which is
+  //    rewritten only after them), then the chain state
+#pragma unroll
+  for (int j = 0; j < kMaxD; ++j) {
+    const int it = ma.it0 + j;
+    if (j >= D || it <= ma.burnin) continue;
+    const double* src = keep[j] >= 0 ? ta.node_th + (int64_t)keep[j] * P * W : ma.theta;
+    double* row = ma.samples + (int64_t)(it - ma.row0) * PS * W;
+    for (int q = 0; q < P; ++q) Row(row + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
+    Row(row + (int64_t)P * W, W).st(off, cj[j]);
+    Row(row + (int64_t)(P + 1) * W, W).st(off, rj[j]);
+    Row(row + (int64_t)(P + 2) * W, W).st(off, aj[j]);
+    Row(row + (int64_t)(P + 3) * W, W).st(off, (double)it);
+    Row(row + (int64_t)(P + 4) * W, W).st(off, nj[j] / (double)it);
+  }
+  if (last >= 0) {
+    const double* src = ta.node_th + (int64_t)last * P * W;
+    for (int q = 0; q < P; ++q) Row(ma.theta + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
+    if (ma.status) ma.status[w] = ta.node_st[(int64_t)last * W + w];
+  }
+  // linked initial states follow the current parameters (k_mh stores them every iteration:
+  // the same final values)
+  if (ma.any_walk) {
+    const double* src = last >= 0 ? ta.node_th + (int64_t)last * P * W : ma.theta;
+    for (int s = 0; s < S; ++s) {
+      const int pi = ma.init_param[s];
+      if (pi >= 0) Row(ma.y0 + (int64_t)s * W, W).st(off, Row(src + (int64_t)pi * W, W).ld(off));
+    }
+  }
+  Row(cur, W).st(off, chi);
+  Row(cur + W, W).st(off, rsq);
+  Row(cur + 2 * W, W).st(off, aic);
+  Row(cur + 3 * W, W).st(off, nacc);
+}
+
+// The same resolution with one wave per chain, for trees of up to 4 095 nodes (depth <= 12):
+// the wave loads the chain's node chis into LDS at once, lane 0 walks them (no dependent
+// global load per level), then lane j writes iteration j's sample row.  Same arithmetic,
+// same outputs as k_mh_resolve.
+__global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S) {
+  using namespace oe;
+  constexpr int kMaxD = kResolveLdsDepth;
+  __shared__ double s_chi[(1 << kMaxD) - 1];
+  __shared__ double s_u[kMaxD], s_c[kMaxD], s_r[kMaxD], s_a[kMaxD], s_n[kMaxD];
+  __shared__ int32_t s_keep[kMaxD];
+  __shared__ int32_t s_last;
+  const MHArgs& ma = ta.m;
+  const int64_t W = ma.W;
+  const int64_t w = blockIdx.x;
+  const int t = threadIdx.x;
+  const int P = pb.P;
+  const int PS = P + 5;
+  const int D = ta.depth;
+  const int N = (1 << D) - 1;
+  const uint32_t off = (uint32_t)w * 8u;
+  for (int n = t; n < N; n += 64) s_chi[n] = ta.node_chi[(int64_t)n * W + w];
+  if (t < D) s_u[t] = Row(ma.u + (int64_t)(ma.it0 + t - ma.draw_it0) * W, W).ld(off);
+  __syncthreads();
+  if (t == 0) {
+    double* cur = ma.cur;
+    double chi = Row(cur, W).ld(off), rsq = Row(cur + W, W).ld(off), aic = Row(cur + 2 * W, W).ld(off);
+    double nacc = Row(cur + 3 * W, W).ld(off);
+    uint32_t path = 0;
+    int32_t last = -1;
+    for (int j = 0; j < D; ++j) {
+      const int n = (1 << j) - 1 + (int)path;
+      const double chin = s_chi[n];
+      const double lr = exp(chi - chin);
+      const double accp = exp(log(lr));
+      const bool acc = accp > s_u[j];
+      if (acc) {
+        chi = chin;
+        rsq = 1.0 - ta.node_ss[(int64_t)n * W + w] / pb.sstot;
+        aic = -2.0 * (-chi) + 2.0 * (double)pb.pnum;
+        nacc += 1.0;
+        last = n;
+      }
+      s_c[j] = chi;
+      s_r[j] = rsq;
+      s_a[j] = aic;
+      s_n[j] = nacc;
+      s_keep[j] = last;
+      path |= (acc ? 1u : 0u) << j;
+    }
+    s_last = last;
+    Row(cur, W).st(off, chi);
+    Row(cur + W, W).st(off, rsq);
+    Row(cur + 2 * W, W).st(off, aic);
+    Row(cur + 3 * W, W).st(off, nacc);
+    if (last >= 0 && ma.status) ma.status[w] = ta.node_st[(int64_t)last * W + w];
+  }
+  __syncthreads();
+  if (t < D) {  // iteration t's sample row (θ from the node the chain holds, or θ not yet rewritten)
+    const int it = ma.it0 + t;
+    if (it > ma.burnin) {
+      const int k = s_keep[t];
+      const double* src = k >= 0 ? ta.node_th + (int64_t)k * P * W : ma.theta;
+      double* row = ma.samples + (int64_t)(it - ma.row0) * PS * W;
+      for (int q = 0; q < P; ++q) Row(row + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
+      Row(row + (int64_t)P * W, W).st(off, s_c[t]);
+      Row(row + (int64_t)(P + 1) * W, W).st(off, s_r[t]);
+      Row(row + (int64_t)(P + 2) * W, W).st(off, s_a[t]);
+      Row(row + (int64_t)(P + 3) * W, W).st(off, (double)it);
+      Row(row + (int64_t)(P + 4) * W, W).st(off, s_n[t] / (double)it);
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    const int32_t last = s_last;
+    if (last >= 0) {
+      const double* src = ta.node_th + (int64_t)last * P * W;
+      for (int q = 0; q < P; ++q) Row(ma.theta + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
+    }
+    if (ma.any_walk) {
+      const double* src = last >= 0 ? ta.node_th + (int64_t)last * P * W : ma.theta;
+      for (int s = 0; s < S; ++s) {
+        const int pi = ma.init_param[s];
+        if (pi >= 0) Row(ma.y0 + (int64_t)s * W, W).st(off, Row(src + (int64_t)pi * W, W).ld(off));
+      }
+    }
+  }
+}

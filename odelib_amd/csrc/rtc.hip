@@ -13,6 +13,7 @@
 #include <hip/hiprtc.h>
 
 #include <cstdio>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -22,29 +23,38 @@
 
 namespace oe {
 
-static const char* kMethodName[5] = {"0", "1", "2", "3", "4"};
 static const char* kBool[2] = {"false", "true"};
 
-std::string rtc_integrate_name(int method, int traj, int nt) {
-  return std::string("oe::k_integrate<UserModel, ") + kMethodName[method] + ", " + kBool[traj] + ", " + kBool[nt] + ">";
-}
-std::string rtc_mh_name(int method) { return std::string("oe::k_mh<UserModel, ") + kMethodName[method] + ">"; }
-std::string rtc_mh_init_name(int method) {
-  return std::string("oe::k_mh<UserModel, ") + kMethodName[method] + ", true>";
-}
-std::string rtc_mh_tree_name(int method) {
-  return std::string("oe::k_mh_tree<UserModel, ") + kMethodName[method] + ">";
-}
-std::string rtc_stiff_wave_name(int traj, int nt) {
-  return std::string("oe::k_stiff_wave<UserModel, ") + kBool[traj] + ", " + kBool[nt] + ">";
-}
-static bool has_stiff_wave(int S, RtcPart part) { return part == kRtcStiff && S > kStiffRegS; }
 // k_mh's iteration loop for method m (ode_kernels.cuh kMhRoundsOnly: the stiff methods of
 // register-path models run their chains as k_mh_tree rounds only)
-static bool has_mh_loop(int S, int m) { return !((m == 2 || m == 4) && S <= kStiffRegS); }
-static int first_method(RtcPart part) { return part == kRtcStiff ? 2 : 0; }
-// the methods of a part: RK4 + DOPRI5; auto + Rosenbrock (+ BDF up to kStiffRegS states)
-static int end_method(int S, RtcPart part) { return part == kRtcStiff ? (S <= kStiffRegS ? 5 : 4) : 2; }
+static bool has_mh_loop(int S, int m) { return !((m == kAuto || m == kBdf) && S <= kStiffRegS); }
+
+// The kernels of a part — RK4 + DOPRI5; auto + Rosenbrock (+ BDF up to kStiffRegS states, +
+// k_stiff_wave above) — each visited as f(name expression, type of its second parameter, its
+// slot in e).  The one list behind the generated instantiations, the name expressions and
+// the module lookups.
+template <class F>
+static bool for_each_kernel(int S, RtcPart part, Entry& e, F&& f) {
+  const bool stiff = part == kRtcStiff;
+  const int m0 = stiff ? kAuto : kRK4, m1 = stiff ? (S <= kStiffRegS ? kBdf : kRosenbrock) : kDOPRI5;
+  for (int m = m0; m <= m1; ++m) {
+    const std::string mm = "<UserModel, " + std::to_string(m);
+    for (int tr = 0; tr < 2; ++tr)
+      for (int nt = 0; nt < 2; ++nt)
+        if (!f("oe::k_integrate" + mm + ", " + kBool[tr] + ", " + kBool[nt] + ">", "IntegrateArgs", e.integrate[m][tr][nt]))
+          return false;
+    if (has_mh_loop(S, m) && !f("oe::k_mh" + mm + ">", "MHArgs", e.mh[m])) return false;
+    if (!f("oe::k_mh" + mm + ", true>", "MHArgs", e.mh_init[m])) return false;
+    if (!f("oe::k_mh_tree" + mm + ">", "MHTreeArgs", e.mh_tree[m])) return false;
+  }
+  if (stiff && S > kStiffRegS)
+    for (int tr = 0; tr < 2; ++tr)
+      for (int nt = 0; nt < 2; ++nt)
+        if (!f(std::string("oe::k_stiff_wave<UserModel, ") + kBool[tr] + ", " + kBool[nt] + ">", "StiffWaveArgs",
+               e.stiff_wave[tr][nt]))
+          return false;
+  return true;
+}
 
 std::string rtc_source(const std::string& body, int S, int P, RtcPart part) {
   std::string src;
@@ -58,24 +68,17 @@ std::string rtc_source(const std::string& body, int S, int P, RtcPart part) {
   src += "    (void)t;\n";
   src += body;
   src += "\n  }\n};\n";
-  for (int m = first_method(part); m < end_method(S, part); ++m) {
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt)
-        src += "template __global__ void " + rtc_integrate_name(m, tr, nt) + "(const oe::DevProblem, const oe::IntegrateArgs);\n";
-    if (has_mh_loop(S, m)) src += "template __global__ void " + rtc_mh_name(m) + "(const oe::DevProblem, const oe::MHArgs);\n";
-    src += "template __global__ void " + rtc_mh_init_name(m) + "(const oe::DevProblem, const oe::MHArgs);\n";
-    src += "template __global__ void " + rtc_mh_tree_name(m) + "(const oe::DevProblem, const oe::MHTreeArgs);\n";
-  }
-  if (has_stiff_wave(S, part))
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt)
-        src += "template __global__ void " + rtc_stiff_wave_name(tr, nt) +
-               "(const oe::DevProblem, const oe::StiffWaveArgs);\n";
+  Entry none{};
+  for_each_kernel(S, part, none, [&](const std::string& name, const char* args, Kernel&) {
+    src += "template __global__ void " + name + "(const oe::DevProblem, const oe::" + args + ");\n";
+    return true;
+  });
   return src;
 }
 
-static int compile_program(const std::string& src, const char* arch, std::vector<std::string>& names,
-                           std::vector<std::string>& lowered, std::vector<char>& code, std::string& log) {
+// lowered: name expression -> the kernel's symbol in the code object
+static int compile_program(const std::string& src, const char* arch, const std::vector<std::string>& names,
+                           std::map<std::string, std::string>& lowered, std::vector<char>& code, std::string& log) {
   hiprtcProgram prog;
   if (hiprtcCreateProgram(&prog, src.c_str(), "odelib_user_rhs.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
     log = "hiprtcCreateProgram failed";
@@ -93,7 +96,6 @@ static int compile_program(const std::string& src, const char* arch, std::vector
     hiprtcDestroyProgram(&prog);
     return -1;
   }
-  lowered.clear();
   for (auto& n : names) {
     const char* lw = nullptr;
     if (hiprtcGetLoweredName(prog, n.c_str(), &lw) != HIPRTC_SUCCESS || !lw) {
@@ -101,7 +103,7 @@ static int compile_program(const std::string& src, const char* arch, std::vector
       hiprtcDestroyProgram(&prog);
       return -1;
     }
-    lowered.emplace_back(lw);
+    lowered[n] = lw;
   }
   size_t cs = 0;
   hiprtcGetCodeSize(prog, &cs);
@@ -111,29 +113,19 @@ static int compile_program(const std::string& src, const char* arch, std::vector
   return 0;
 }
 
-static std::vector<std::string> all_names(int S, RtcPart part) {
-  std::vector<std::string> names;
-  const int m0 = first_method(part);
-  for (int m = m0; m < end_method(S, part); ++m)
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt) names.push_back(rtc_integrate_name(m, tr, nt));
-  for (int m = m0; m < end_method(S, part); ++m)
-    if (has_mh_loop(S, m)) names.push_back(rtc_mh_name(m));
-  for (int m = m0; m < end_method(S, part); ++m) names.push_back(rtc_mh_init_name(m));
-  for (int m = m0; m < end_method(S, part); ++m) names.push_back(rtc_mh_tree_name(m));
-  if (has_stiff_wave(S, part))
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt) names.push_back(rtc_stiff_wave_name(tr, nt));
-  return names;
-}
-
 int rtc_build(const std::string& body, int S, int P, const char* arch, RtcPart part, RtcModule* out,
-              std::string& err) {
+              Entry* entry, std::string& err) {
   if (part == kRtcStiff && S > kStiffMaxS) {
     err = "the stiff methods (auto, rosenbrock) need n_states <= " + std::to_string(kStiffMaxS);
     return -1;
   }
-  std::vector<std::string> names = all_names(S, part), lowered;
+  Entry none{};
+  std::vector<std::string> names;
+  for_each_kernel(S, part, none, [&](const std::string& name, const char*, Kernel&) {
+    names.push_back(name);
+    return true;
+  });
+  std::map<std::string, std::string> lowered;
   std::vector<char> code;
   std::string log;
   if (compile_program(rtc_source(body, S, P, part), arch, names, lowered, code, log)) {
@@ -150,29 +142,12 @@ int rtc_build(const std::string& body, int S, int P, const char* arch, RtcPart p
     return -1;
   }
   (part == kRtcStiff ? out->stiff_mod : out->mod) = mod;
-  size_t idx = 0;
-  const int m0 = first_method(part);
-  auto get = [&](hipFunction_t* f) {
-    if (hipModuleGetFunction(f, mod, lowered[idx++].c_str()) != hipSuccess) {
-      err = "hipModuleGetFunction failed for the user RHS";
-      return false;
-    }
-    return true;
-  };
-  for (int m = m0; m < end_method(S, part); ++m)
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt)
-        if (!get(&out->integrate[m][tr][nt])) return -1;
-  for (int m = m0; m < end_method(S, part); ++m)
-    if (has_mh_loop(S, m) && !get(&out->mh[m])) return -1;
-  for (int m = m0; m < end_method(S, part); ++m)
-    if (!get(&out->mh_init[m])) return -1;
-  for (int m = m0; m < end_method(S, part); ++m)
-    if (!get(&out->mh_tree[m])) return -1;
-  if (has_stiff_wave(S, part))
-    for (int tr = 0; tr < 2; ++tr)
-      for (int nt = 0; nt < 2; ++nt)
-        if (!get(&out->stiff_wave[tr][nt])) return -1;
+  if (!for_each_kernel(S, part, *entry, [&](const std::string& name, const char*, Kernel& slot) {
+        return hipModuleGetFunction(&slot.mod, mod, lowered.at(name).c_str()) == hipSuccess;
+      })) {
+    err = "hipModuleGetFunction failed for the user RHS";
+    return -1;
+  }
   if (part == kRtcStiff) out->stiff = 1;
   return 0;
 }

@@ -43,6 +43,13 @@ def test_rk_ref_under_msan():
     assert r.returncode == 0 and "SANITIZE OK" in r.stdout, r.stderr[-4000:]
 
 
+def test_launch_plans_under_asan_ubsan():
+    """The C-ABI's launch plans (launch_plan.h: grids, queue placement, speculation depth, chunk
+    and buffer sizes as pure functions) over a grid of shapes, and hand-derived values."""
+    r = subprocess.run([_exe("plan_asan")], env=ENV, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "SANITIZE OK" in r.stdout, (r.stdout[-4000:], r.stderr[-4000:])
+
+
 def test_c_abi_host_code_under_asan_ubsan_error_paths():
     r = subprocess.run([_exe("capi_asan")], env=ENV, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "SANITIZE OK" in r.stdout, r.stderr[-4000:]

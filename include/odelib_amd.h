@@ -19,6 +19,9 @@
  *   oe_mh_run        <- Statistics/Samplers.py:53-174 MetropolisHastings, for W
  *                       independent chains (one per walker), i.e. the
  *                       MCMC(...) chain loop of Framework.py:1013-1030.
+ *   oe_band_*        <- plot_uncertainty (Framework.py:734-740), which overlays 100 random
+ *                       posterior rows: here every row is summarised (count, log-space
+ *                       moments, min, max, quantiles per grid time and output column).
  *   oe_allgather_samples <- the pd.concat of the per-process chain posteriors
  *                       (Framework.py:1035-1038) after Pool.starmap (:779-780):
  *                       one RCCL all-gather of the ranks' sample blocks.
@@ -45,7 +48,7 @@
 extern "C" {
 #endif
 
-#define OE_ABI_VERSION 6
+#define OE_ABI_VERSION 7
 
 /* return codes */
 enum {
@@ -325,6 +328,41 @@ int oe_pool_pad(int64_t rows, const double* block, int64_t count, int64_t cmax, 
                 uint32_t flags);
 int oe_pool_relayout(int32_t n_ranks, int64_t rows, const int64_t* counts, const double* gathered, double* out,
                      void* hip_stream, uint32_t flags);
+
+/* ---- posterior predictive bands (ABI 7): reductions across walkers ----------------------
+ * A posterior of any number of rows is streamed through oe_integrate in chunks; each chunk's
+ * trajectory traj [T][S][W] is folded into accumulators of O(T * n_cols * n_bins), T and S
+ * being those of the problem set in the context.  Column c is the bitmask col_mask[c] of
+ * states (as oe_problem.obs_mask): C = sum of the states in increasing order; an element is
+ * valid iff C is finite and > 0; l = log C.  Per (grid index, column) over the valid elements
+ * of every chunk folded so far:
+ *   acc  [T][n_cols][5] doubles: n, mean of l, M2 of l (sum of squared deviations: Welford
+ *        per lane, Chan merges in a fixed order, no floating-point atomics), min C, max C;
+ *   hist [T][n_cols][n_bins] uint32: counts of l in n_bins equal bins on [log min, log max],
+ *        bin = clamp((int)((l - lo) / w), 0, n_bins - 1), everything in bin 0 when max == min;
+ *   quantile q of C: r = q (n - 1), k = floor(r); rank j, in the bin b holding ranks
+ *        [c0, c0 + m), sits at lo + w (b + (j - c0 + 1/2) / m); the estimate interpolates the
+ *        positions of ranks k and min(k + 1, n - 1) with weight r - k, is exponentiated and
+ *        clamped to [min, max], so log x_(k) - w <= log estimate <= log x_(k+1) + w.
+ *        n == 0: NaN; max == min: that value.
+ * Order of calls: oe_band_begin; oe_band_moments for every chunk; then (min and max are final)
+ * oe_band_hist for every chunk again; oe_band_quantiles.  n, min, max, hist and the quantiles
+ * are the same bits for any chunking; mean and M2 are the same bits run to run for one
+ * chunking and agree across chunkings to rounding.  The accumulators of several ranks merge:
+ * integer sums for n and hist, a Chan merge for the moments, min / max.
+ * Device pointers only (col_mask and q are host arrays); launched on the context's stream;
+ * synchronous on return unless OE_ASYNC (oe_band_begin: always synchronous).
+ * OE_ERR_STATE before oe_problem_set, or before oe_band_begin (oe_problem_set ends a band);
+ * OE_ERR_ARG: a null pointer, n_cols outside 1..64, a zero mask or one with bits at or above
+ * S, n_bins outside 2..4096, n_q outside 1..64, a q outside [0, 1], n_walkers < 1. */
+int oe_band_begin(oe_ctx* ctx, int32_t n_cols, const uint64_t* col_mask, int32_t n_bins, double* acc,
+                  uint32_t* hist);
+int oe_band_moments(oe_ctx* ctx, int64_t n_walkers, const double* traj, double* acc, uint32_t flags);
+int oe_band_hist(oe_ctx* ctx, int64_t n_walkers, const double* traj, const double* acc, uint32_t* hist,
+                 uint32_t flags);
+/* out [n_q][T][n_cols] */
+int oe_band_quantiles(oe_ctx* ctx, const double* acc, const uint32_t* hist, int32_t n_q, const double* q,
+                      double* out, uint32_t flags);
 
 /* Device time (ms) of the kernel launches of the last oe_integrate / oe_mh_run,
  * from HIP events recorded on the context's stream around them (waits for them). */

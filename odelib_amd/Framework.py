@@ -134,6 +134,28 @@ def _worker_order(n_rows: int, cores: int):
     return np.asarray(order, dtype=np.int64), np.asarray(index, dtype=np.int64)
 
 
+def band_inputs(pnames, snames, inits, posteriors):
+    """Posterior rows -> the engine's (theta [P][W], y0 [S][W]).  ``posteriors``: a DataFrame
+    with the ``pnames`` columns (others are ignored) or a [W][P] array in ``pnames`` order.
+    A '<state>0' parameter sets that state's initial value for its row, as the MH kernels'
+    ``init_param`` does (Samplers.py:110-114); the other states start at ``inits``."""
+    pnames, snames = list(pnames), list(snames)
+    if isinstance(posteriors, pd.DataFrame):
+        rows = posteriors[pnames].to_numpy(dtype=float)
+    else:
+        rows = np.asarray(posteriors, dtype=float)
+        if rows.ndim != 2 or rows.shape[1] != len(pnames):
+            raise ValueError(f"posteriors must be [W][{len(pnames)}] (columns {', '.join(pnames)})")
+    if len(rows) == 0:
+        raise ValueError("posteriors has no rows")
+    theta = np.ascontiguousarray(rows.T)
+    y0 = np.repeat(np.asarray(inits, dtype=float).reshape(len(snames), 1), len(rows), axis=1)
+    for s, name in enumerate(snames):
+        if name + '0' in pnames:
+            y0[s] = theta[pnames.index(name + '0')]
+    return theta, y0
+
+
 class ModelFramework:
     """ODE model + data + priors (Framework.py:166-1166), computed on MI355X."""
 
@@ -434,6 +456,51 @@ class ModelFramework:
             self.set_parameters(**row)
             traj = self.integrate()
             ax.plot(traj.time, traj[variable], c=str(0.8), lw=1, zorder=1)
+
+    def _band_masks(self):
+        """One state bitmask per output column (``get_snames(after_summation=True)`` order),
+        built as ``fit_problem`` builds ``obs_mask``."""
+        keep = self._sumkeep if self._summations_index else tuple(range(len(self._snames)))
+        masks = []
+        for orig in keep:
+            bits = 0
+            for s in self._summations_index.get(orig, (orig,)):
+                bits |= (1 << s)
+            masks.append(bits)
+        return np.asarray(masks, dtype=np.uint64)
+
+    def predict_band(self, posteriors, quantiles=(0.025, 0.5, 0.975), n_bins=1024, chunk=None):
+        """The posterior predictive band of every output column: all rows of ``posteriors``
+        (DataFrame with the parameter columns, or [W][P] array) are integrated on the device
+        in chunks and summarised there (``Engine.band``; nothing of size rows x times is
+        kept).  A '<state>0' parameter sets that state's initial value per row.  Returns a
+        long DataFrame, one row per output column (``get_snames(after_summation=True)`` order)
+        and grid time: time, organism, n (rows with a finite positive value), mean_log, sd_log
+        (mean and population sd of the log), min, max, and one ``q<quantile>`` column each."""
+        theta, y0 = band_inputs(self._pnames, self._snames, self.get_inits(), posteriors)
+        res = self.engine().band(y0, theta, quantiles, n_bins=n_bins, chunk=chunk, col_masks=self._band_masks())
+        names = self.get_snames(after_summation=True)
+        T = len(self.times)
+        out = {"time": np.tile(self.times, len(names)), "organism": np.repeat(names, T)}
+        for k in ("n", "mean_log", "sd_log", "min", "max"):
+            out[k] = res[k].T.reshape(-1)
+        for j, q in enumerate(np.asarray(quantiles, dtype=float).reshape(-1)):
+            out[f"q{q:g}"] = res["q"][j].T.reshape(-1)
+        df = pd.DataFrame(out)
+        df.attrs["status_or"], df.attrs["n_status"] = res["status_or"], res["n_status"]
+        return df
+
+    def plot_band(self, ax, posteriors, variable, quantiles=(0.025, 0.975)):
+        """Shade the band between the outer ``quantiles`` of ``variable`` over all posterior
+        rows and draw the median (``predict_band``)."""
+        lo, hi = min(quantiles), max(quantiles)
+        band = self.predict_band(posteriors, quantiles=(lo, 0.5, hi))
+        b = band[band["organism"] == variable]
+        if b.empty:
+            raise ValueError(f"unknown variable {variable!r}; the columns are {', '.join(self.get_snames())}")
+        ax.fill_between(b["time"], b[f"q{lo:g}"], b[f"q{hi:g}"], color=str(0.8), zorder=1)
+        ax.plot(b["time"], b["q0.5"], c=str(0.3), lw=1, zorder=2)
+        return band
 
     # ------------------------------------------------------------------ LHS survey
     def _lhs_samples(self, samples=100, **kwargs):

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ODELIB_AMD_LIB", os.path.join(_HERE, "csrc", "libodelib_amd.so"))
 
 # --- constants mirrored from include/odelib_amd.h -----------------------------------
-OE_ABI_VERSION = 6
+OE_ABI_VERSION = 7
 OE_COMM_ID_BYTES = 128
 OE_OK = 0
 OE_ERR_ARG, OE_ERR_HIP, OE_ERR_STATE, OE_ERR_UNSUPPORTED, OE_ERR_NOMEM = -1, -2, -3, -4, -5
@@ -58,6 +58,10 @@ EXPORTED = (
     "oe_last_variant",
     "oe_tune_times",
     "oe_last_mh_depth",
+    "oe_band_begin",
+    "oe_band_moments",
+    "oe_band_hist",
+    "oe_band_quantiles",
 )
 
 
@@ -192,6 +196,14 @@ def load_library(path: str | None = None):
         lib.oe_last_mh_depth.argtypes = [vp, C.POINTER(i32)]
         lib.oe_tune_times.restype = C.c_int
         lib.oe_tune_times.argtypes = [vp, C.POINTER(C.c_double), i32]
+        lib.oe_band_begin.restype = C.c_int
+        lib.oe_band_begin.argtypes = [vp, i32, vp, i32, vp, vp]
+        lib.oe_band_moments.restype = C.c_int
+        lib.oe_band_moments.argtypes = [vp, i64, vp, vp, u32]
+        lib.oe_band_hist.restype = C.c_int
+        lib.oe_band_hist.argtypes = [vp, i64, vp, vp, vp, u32]
+        lib.oe_band_quantiles.restype = C.c_int
+        lib.oe_band_quantiles.argtypes = [vp, vp, vp, i32, vp, vp, u32]
         if lib.oe_abi_version() != OE_ABI_VERSION:
             raise NativeUnavailable("libodelib_amd.so ABI version mismatch; rebuild it")
         if path is None:
@@ -264,6 +276,26 @@ class Context:
     def numpy_streams(self, n_walkers, seeds, nits, n_params, walk_mask, prior_draws, step_sd, dz, u):
         self._check(self.lib.oe_numpy_streams(self._h, int(n_walkers), seeds, int(nits), int(n_params), walk_mask,
                                               int(prior_draws), float(step_sd), dz, u), "oe_numpy_streams")
+
+    def band_begin(self, col_masks, n_bins, acc, hist):
+        """``oe_band_begin``: ``col_masks`` a host uint64 array, ``acc`` / ``hist`` device pointers."""
+        import numpy as np
+        m = np.ascontiguousarray(np.asarray(col_masks, dtype=np.uint64))
+        self._check(self.lib.oe_band_begin(self._h, len(m), C.c_void_p(m.ctypes.data), int(n_bins), acc, hist),
+                    "oe_band_begin")
+
+    def band_moments(self, n_walkers, traj, acc, flags=0):
+        self._check(self.lib.oe_band_moments(self._h, int(n_walkers), traj, acc, int(flags)), "oe_band_moments")
+
+    def band_hist(self, n_walkers, traj, acc, hist, flags=0):
+        self._check(self.lib.oe_band_hist(self._h, int(n_walkers), traj, acc, hist, int(flags)), "oe_band_hist")
+
+    def band_quantiles(self, acc, hist, q, out, flags=0):
+        """``oe_band_quantiles``: ``q`` a host float64 array, the rest device pointers."""
+        import numpy as np
+        qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
+        self._check(self.lib.oe_band_quantiles(self._h, acc, hist, len(qa), C.c_void_p(qa.ctypes.data), out,
+                                               int(flags)), "oe_band_quantiles")
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "band.cuh"
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
 
@@ -15,3 +16,9 @@ __global__ void __launch_bounds__(oe::kNpChainsPerBlock) k_np_draws(const oe::Np
 __global__ void __launch_bounds__(256) k_philox_draws(const oe::DrawArgs d);
 __global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S);
 __global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S);
+// posterior predictive bands (band.cuh): reductions across the walkers of a trajectory chunk
+__global__ void __launch_bounds__(256) k_band_init(double* __restrict__ acc, int64_t n_cells);
+__global__ void __launch_bounds__(oe::kBandBlock) k_band_moments(const oe::BandArgs a);
+__global__ void __launch_bounds__(256) k_band_merge(const oe::BandArgs a);
+__global__ void __launch_bounds__(oe::kBandBlock) k_band_hist(const oe::BandArgs a);
+__global__ void __launch_bounds__(256) k_band_quantiles(const oe::BandQArgs a);

@@ -58,7 +58,7 @@ using plan::kMaxWalkers;
 // launch_plan.h restates the device headers' constants (it includes none of them)
 static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRegS &&
                   plan::kHandBdfWaves == kHandBdfWaves && plan::kResolveLdsDepth == kResolveLdsDepth &&
-                  plan::kBlock == kMhBlock,
+                  plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile,
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -116,7 +116,16 @@ struct oe_ctx {
   DevBuf tree;      // speculative MH rounds: node proposals and results
   DevBuf obs;       // the per-lane BDF pass's deferred observations, [n_obs][lanes] (DevProblem::obs_c)
   DevBuf hq;        // the hand-over queue, below
-  std::array<DevBuf*, 7> bufs() { return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq}; }
+  DevBuf band_part;  // k_band_moments' partials, one cell per workgroup and column
+  DevBuf band_tab;   // the band's column masks [64] uint64, then its quantiles [64] doubles
+  std::array<DevBuf*, 9> bufs() {
+    return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab};
+  }
+  // posterior bands (oe_band_begin .. oe_band_quantiles); the tables' host copies live here so
+  // an asynchronous upload never reads the caller's arrays after the call
+  int32_t band_cols = 0, band_bins = 0;  // 0: no band begun for the current problem
+  uint64_t band_masks[kBandMaxCols] = {};
+  double band_q[kBandMaxQ] = {};
   // numpy draws of MH chunk j + 1 run on a side stream while chunk j's MH kernels run (one
   // 64-chain block per CU beside them), into the other half of `draws`
   hipStream_t np_stream = nullptr;
@@ -618,6 +627,7 @@ int oe_problem_set(oe_ctx* c, const oe_problem* p) {
   c->method = p->method;
   c->entry = e;
   c->has_problem = true;
+  c->band_cols = c->band_bins = 0;  // a band belongs to the problem it was begun for
   c->err.clear();
   return OE_OK;
 }
@@ -1004,6 +1014,145 @@ int oe_numpy_streams(oe_ctx* c, int64_t W, const uint32_t* seeds, int32_t nits, 
   c->timed = true;
   OE_HIP(c, hipStreamSynchronize(c->stream));
   return OE_OK;
+}
+
+// ---- posterior predictive bands (band.cuh) ----------------------------
+namespace {
+
+// what the three calls after oe_band_begin share: a problem set and a band begun
+int band_state(oe_ctx* c, const char* who) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!c->has_problem) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_problem_set first");
+  if (!c->band_cols) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_band_begin first");
+  return OE_OK;
+}
+
+// workgroups of the reduce passes per CU: 16, or OE_BAND_WG_PER_CU (measurements)
+int band_cus(const oe_ctx* c) {
+  static const long n = [] {
+    const char* v = getenv("OE_BAND_WG_PER_CU");
+    return v ? strtol(v, nullptr, 10) : 0;
+  }();
+  return n > 0 ? (int)std::max<long>(1, (long)c->n_cu * n / 16) : c->n_cu;
+}
+
+BandArgs band_args(oe_ctx* c, const plan::BandPlan& pl, int64_t W, const double* traj, double* acc, uint32_t* hist) {
+  BandArgs a{};
+  a.traj = traj;
+  a.masks = static_cast<const uint64_t*>(c->band_tab.p);
+  a.acc = acc;
+  a.part = static_cast<double*>(c->band_part.p);
+  a.hist = hist;
+  a.W = W;
+  a.per_block = pl.per_block;
+  a.T = c->dp.T;
+  a.S = c->entry->S;
+  a.n_cols = c->band_cols;
+  a.n_bins = c->band_bins;
+  a.bpr = pl.blocks_per_row;
+  return a;
+}
+
+int band_finish(oe_ctx* c, uint32_t flags) {
+  OE_HIP(c, hipGetLastError());
+  OE_HIP(c, hipEventRecord(c->ev1, c->stream));
+  c->timed = true;
+  if (!(flags & OE_ASYNC)) OE_HIP(c, hipStreamSynchronize(c->stream));
+  return OE_OK;
+}
+
+}  // namespace
+
+int oe_band_begin(oe_ctx* c, int32_t n_cols, const uint64_t* col_mask, int32_t n_bins, double* acc, uint32_t* hist) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!c->has_problem) return fail(c, OE_ERR_STATE, "oe_band_begin: call oe_problem_set first");
+  if (!col_mask || !acc || !hist) return fail(c, OE_ERR_ARG, "oe_band_begin: col_mask, acc and hist are required");
+  if (n_cols < 1 || n_cols > kBandMaxCols) return fail(c, OE_ERR_ARG, "oe_band_begin: n_cols must be in [1, 64]");
+  if (n_bins < 2 || n_bins > kBandMaxBins) return fail(c, OE_ERR_ARG, "oe_band_begin: n_bins must be in [2, 4096]");
+  const int S = c->entry->S, T = c->dp.T;
+  const uint64_t valid_mask = (S >= 64) ? ~0ull : ((1ull << S) - 1ull);
+  for (int k = 0; k < n_cols; ++k)
+    if (col_mask[k] == 0 || (col_mask[k] & ~valid_mask))
+      return fail(c, OE_ERR_ARG, "oe_band_begin: a column mask selects no / unknown states");
+  OE_DEVICE_GUARD(c);
+  c->band_cols = c->band_bins = 0;
+  const int rc = c->band_tab.reserve(c, sizeof(uint64_t) * kBandMaxCols + sizeof(double) * kBandMaxQ);
+  if (rc) return rc;
+  // (the stream may still read the last band's tables: order the host copy's rewrite after it)
+  OE_HIP(c, hipStreamSynchronize(c->stream));
+  std::memset(c->band_masks, 0, sizeof(c->band_masks));
+  std::memcpy(c->band_masks, col_mask, sizeof(uint64_t) * (size_t)n_cols);
+  OE_HIP(c, hipMemcpyAsync(c->band_tab.p, c->band_masks, sizeof(c->band_masks), hipMemcpyHostToDevice, c->stream));
+  const int64_t cells = (int64_t)T * n_cols;
+  OE_HIP(c, launch(kernel_of(k_band_init), dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), c->stream, acc,
+                   cells));
+  OE_HIP(c, hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)cells * (size_t)n_bins, c->stream));
+  OE_HIP(c, hipGetLastError());
+  OE_HIP(c, hipStreamSynchronize(c->stream));
+  c->band_cols = n_cols;
+  c->band_bins = n_bins;
+  return OE_OK;
+}
+
+int oe_band_moments(oe_ctx* c, int64_t W, const double* traj, double* acc, uint32_t flags) {
+  int rc = band_state(c, "oe_band_moments");
+  if (rc) return rc;
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_moments: device pointers only");
+  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_band_moments: n_walkers must be in [1, 2^29]");
+  if (!traj || !acc) return fail(c, OE_ERR_ARG, "oe_band_moments: traj and acc are required");
+  OE_DEVICE_GUARD(c);
+  const plan::BandPlan pl = plan::plan_band_reduce(c->dp.T, W, c->band_cols, band_cus(c));
+  rc = c->band_part.reserve(c, pl.partial_bytes);
+  if (rc) return rc;
+  const BandArgs a = band_args(c, pl, W, traj, acc, nullptr);
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_band_moments), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_band_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
+  return band_finish(c, flags);
+}
+
+int oe_band_hist(oe_ctx* c, int64_t W, const double* traj, const double* acc, uint32_t* hist, uint32_t flags) {
+  const int rc = band_state(c, "oe_band_hist");
+  if (rc) return rc;
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_hist: device pointers only");
+  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_band_hist: n_walkers must be in [1, 2^29]");
+  if (!traj || !acc || !hist) return fail(c, OE_ERR_ARG, "oe_band_hist: traj, acc and hist are required");
+  OE_DEVICE_GUARD(c);
+  const plan::BandPlan pl = plan::plan_band_reduce(c->dp.T, W, c->band_cols, band_cus(c));
+  const BandArgs a = band_args(c, pl, W, traj, const_cast<double*>(acc), hist);
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_band_hist), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  return band_finish(c, flags);
+}
+
+int oe_band_quantiles(oe_ctx* c, const double* acc, const uint32_t* hist, int32_t n_q, const double* q, double* out,
+                      uint32_t flags) {
+  const int rc = band_state(c, "oe_band_quantiles");
+  if (rc) return rc;
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_quantiles: device pointers only");
+  if (!acc || !hist || !q || !out) return fail(c, OE_ERR_ARG, "oe_band_quantiles: acc, hist, q and out are required");
+  if (n_q < 1 || n_q > kBandMaxQ) return fail(c, OE_ERR_ARG, "oe_band_quantiles: n_q must be in [1, 64]");
+  for (int k = 0; k < n_q; ++k)
+    if (!(q[k] >= 0.0 && q[k] <= 1.0)) return fail(c, OE_ERR_ARG, "oe_band_quantiles: q must be in [0, 1]");
+  OE_DEVICE_GUARD(c);
+  // (an earlier asynchronous call may still read the quantile table)
+  OE_HIP(c, hipStreamSynchronize(c->stream));
+  std::memcpy(c->band_q, q, sizeof(double) * (size_t)n_q);
+  double* d_q = reinterpret_cast<double*>(static_cast<char*>(c->band_tab.p) + sizeof(uint64_t) * kBandMaxCols);
+  OE_HIP(c, hipMemcpyAsync(d_q, c->band_q, sizeof(double) * (size_t)n_q, hipMemcpyHostToDevice, c->stream));
+  BandQArgs a{};
+  a.acc = acc;
+  a.hist = hist;
+  a.q = d_q;
+  a.out = out;
+  a.T = c->dp.T;
+  a.n_cols = c->band_cols;
+  a.n_bins = c->band_bins;
+  a.n_q = n_q;
+  const int64_t n = (int64_t)a.T * a.n_cols * n_q;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_band_quantiles), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), c->stream, a));
+  return band_finish(c, flags);
 }
 
 int oe_last_kernel_ms(oe_ctx* c, double* ms) {

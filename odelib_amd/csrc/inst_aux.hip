@@ -1,5 +1,6 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
-// (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution.
+// (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
+// posterior band reductions.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -209,3 +210,12 @@ __global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb,
     }
   }
 }
+
+// posterior predictive bands: the reductions across walkers (band.cuh)
+__global__ void __launch_bounds__(256) k_band_init(double* __restrict__ acc, int64_t n_cells) {
+  oe::band_init(acc, n_cells);
+}
+__global__ void __launch_bounds__(oe::kBandBlock) k_band_moments(const oe::BandArgs a) { oe::band_moments(a); }
+__global__ void __launch_bounds__(256) k_band_merge(const oe::BandArgs a) { oe::band_merge(a); }
+__global__ void __launch_bounds__(oe::kBandBlock) k_band_hist(const oe::BandArgs a) { oe::band_hist(a); }
+__global__ void __launch_bounds__(256) k_band_quantiles(const oe::BandQArgs a) { oe::band_quantiles(a); }

@@ -1,7 +1,8 @@
-// launch_plan.h — what oe_integrate and oe_mh_run launch, decided by pure functions: numbers
-// in, a plan out (kernel, grids, half waves, XCD runs, the hand-over queue's placement,
-// speculation depth, chunk, buffer sizes).  No HIP here, so tests/sanitize/plan_driver.cpp
-// checks the arithmetic on the CPU; capi.hip reserves, fills the arguments and launches.
+// launch_plan.h — what oe_integrate, oe_mh_run and the oe_band_* passes launch, decided by
+// pure functions: numbers in, a plan out (kernel, grids, half waves, XCD runs, the hand-over
+// queue's placement, speculation depth, chunk, buffer sizes).  No HIP here, so
+// tests/sanitize/plan_driver.cpp and band_plan_driver.cpp check the arithmetic on the CPU;
+// capi.hip reserves, fills the arguments and launches.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -297,6 +298,47 @@ inline MhRound plan_mh_round(const MhPlan& p, int64_t W, int n_cu, int it0, int 
   r.rgrid = r.resolve_wave ? (unsigned)W : p.grid;
   r.rblock = r.resolve_wave ? 64 : kBlock;
   return r;
+}
+
+// ---- oe_band_* ----------------------------------------------------------------------
+constexpr int kBandBlock = 256;                        // threads per workgroup of the reduce passes
+constexpr int kBandTile = 1024;                        // walkers per workgroup trip (4 per lane)
+constexpr int64_t kBandBudget = int64_t(1) << 30;      // default resident trajectory chunk: 1 GiB
+
+struct BandPlan {
+  unsigned grid = 0, block = kBandBlock;  // k_band_moments / k_band_hist: grid = T * blocks_per_row
+  int64_t per_block = 0;                  // consecutive walkers of one grid row per workgroup
+  int32_t blocks_per_row = 0;
+  size_t partial_bytes = 0;               // k_band_moments' [T][blocks_per_row][n_cols][5] doubles
+  unsigned cell_grid = 0;                 // k_band_init / k_band_merge: one lane per (row, column)
+};
+
+// The reduce passes over a chunk traj [T][S][W]: workgroup (i, j) folds walkers
+// [j * per_block, min(W, (j + 1) * per_block)) of grid row i.  About 16 workgroups per CU in
+// all (enough rows: one workgroup per row), runs a multiple of kBandTile.
+inline BandPlan plan_band_reduce(int T, int64_t W, int n_cols, int n_cu) {
+  BandPlan p;
+  const int64_t tiles = (W + kBandTile - 1) / kBandTile;
+  const int64_t want = std::max<int64_t>(1, ((int64_t)16 * n_cu + T - 1) / T);
+  const int64_t bpr0 = std::min(tiles, want);
+  const int64_t tiles_per_block = (tiles + bpr0 - 1) / bpr0;
+  p.per_block = tiles_per_block * kBandTile;
+  p.blocks_per_row = (int32_t)((tiles + tiles_per_block - 1) / tiles_per_block);
+  p.grid = (unsigned)((int64_t)T * p.blocks_per_row);
+  p.partial_bytes = sizeof(double) * 5 * (size_t)T * (size_t)p.blocks_per_row * (size_t)n_cols;
+  p.cell_grid = (unsigned)(((int64_t)T * n_cols + kBlock - 1) / kBlock);
+  return p;
+}
+
+// Walkers per trajectory chunk of a posterior of W_total rows: the largest multiple of 256
+// whose [T][S][chunk] doubles fit budget_bytes, at least 256, at most W_total rounded up to
+// 256.  Multiples of 256 keep every 64-walker wave (DOPRI5's lockstep group) and every
+// workgroup where one launch over all rows would put them.
+inline int64_t plan_band_chunk(int T, int S, int64_t W_total, int64_t budget_bytes) {
+  const int64_t per_walker = (int64_t)8 * T * S;
+  const int64_t fit = budget_bytes / per_walker / 256 * 256;
+  const int64_t all = (W_total + 255) / 256 * 256;
+  return std::max<int64_t>(256, std::min(fit, all));
 }
 
 }  // namespace plan

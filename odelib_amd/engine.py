@@ -175,6 +175,29 @@ def check_resume(resume, rec, numpy_seeds=None, allow_unverified=False):
     return numpy_seeds
 
 
+BAND_BUDGET = 1 << 30  # resident trajectory chunk of a band: 1 GiB, as the MH draws' cap
+
+
+def band_chunk(n_times: int, n_states: int, n_walkers: int, budget_bytes: int = BAND_BUDGET) -> int:
+    """Walkers per trajectory chunk of ``Engine.band`` (csrc/launch_plan.h plan_band_chunk,
+    restated): the largest multiple of 256 whose [T][S][chunk] doubles fit the budget, at
+    least 256, at most ``n_walkers`` rounded up to 256."""
+    fit = int(budget_bytes) // (8 * int(n_times) * int(n_states)) // 256 * 256
+    return max(256, min(fit, -(-int(n_walkers) // 256) * 256))
+
+
+def band_summary(acc: np.ndarray) -> dict:
+    """The accumulator cells [T][n_cols][5] (n, mean, M2, min, max) as the arrays ``Engine.band``
+    returns; a cell without a valid element is NaN but for its count."""
+    n = acc[..., 0]
+    some = n > 0
+    nan = np.full(n.shape, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sd = np.sqrt(acc[..., 2] / n)
+    return {"n": n.astype(np.int64), "mean_log": np.where(some, acc[..., 1], nan), "sd_log": np.where(some, sd, nan),
+            "min": np.where(some, acc[..., 3], nan), "max": np.where(some, acc[..., 4], nan)}
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -297,6 +320,75 @@ class Engine:
         if sync:
             torch.cuda.synchronize(self.dev)
         return {"traj": traj, "chi": chi, "ssres": ssres, "status": status}
+
+    # -- posterior predictive bands -------------------------------------------------------------
+    def band(self, y0, theta, quantiles, n_bins: int = 1024, chunk=None, col_masks=None, nt_stores: bool = True):
+        """Summarise the trajectories of every walker (posterior row) per grid time and output
+        column without keeping them: y0 [S][W], theta [P][W] → dict of host
+        arrays ``n`` (int64), ``mean_log``, ``sd_log``, ``min``, ``max`` [T][n_cols] and ``q``
+        [n_q][T][n_cols], plus ``status_or`` (the OR of the walkers' status bits) and
+        ``n_status`` (walkers with a non-zero status).
+
+        ``col_masks``: one state bitmask per column (default: every state its own column).
+        The rows go through ``integrate`` in chunks of ``chunk`` walkers (rounded up to a
+        multiple of 256; default ``band_chunk``: 1 GiB of trajectory) into one reused
+        trajectory buffer.  One chunk: integrate → moments → histogram on that buffer.
+        More: a first pass over the chunks for the moments (min and max fix the histogram's
+        bins), a second that integrates them again for the histogram.  Elements whose column
+        value is not finite and positive are left out (``n`` counts the rest)."""
+        torch = self.torch
+        pb = self.problem
+        T, S = pb.n_times, pb.n_states
+        theta_t = theta if isinstance(theta, torch.Tensor) else np.asarray(theta)
+        W = int(theta_t.shape[1])
+        if W < 1:
+            raise ValueError("band needs at least one walker")
+        y0 = self._dev(y0, (S, W))
+        theta = self._dev(theta, (pb.n_params, W))
+        masks = np.asarray([1 << s for s in range(S)] if col_masks is None else col_masks, dtype=np.uint64)
+        q = np.ascontiguousarray(np.asarray(quantiles, dtype=np.float64).reshape(-1))
+        n_cols, n_q = len(masks), len(q)
+        Wc = band_chunk(T, S, W) if chunk is None else -(-int(chunk) // 256) * 256
+        Wc = min(max(Wc, 256), -(-W // 256) * 256)
+        spans = [(a, min(W, a + Wc)) for a in range(0, W, Wc)]
+        buf = torch.empty(T * S * min(W, Wc), dtype=torch.float64, device=self.dev)
+        acc = torch.empty((T, n_cols, 5), dtype=torch.float64, device=self.dev)
+        hist = torch.empty((T, n_cols, int(n_bins)), dtype=torch.int32, device=self.dev)
+        out = torch.empty((n_q, T, n_cols), dtype=torch.float64, device=self.dev)
+        st_or = torch.zeros((), dtype=torch.int32, device=self.dev)
+        st_n = torch.zeros((), dtype=torch.int64, device=self.dev)
+        self._sync_stream()
+        self.ctx.band_begin(masks, n_bins, _ptr(acc), _ptr(hist))
+
+        def run(a, b, first):
+            w = b - a
+            traj = buf[:T * S * w].view(T, S, w)
+            whole = len(spans) == 1
+            res = self.integrate(y0 if whole else y0[:, a:b], theta if whole else theta[:, a:b], traj_out=traj,
+                                 nt_stores=nt_stores, sync=False, timing=False)
+            if first:
+                st = res["status"]
+                for bit in (1, 2, 4, 8, 16):
+                    st_or.bitwise_or_(((st & bit) != 0).any().to(torch.int32) * bit)
+                st_n.add_((st != 0).sum())
+            return w, traj
+
+        for a, b in spans:
+            w, traj = run(a, b, True)
+            self.ctx.band_moments(w, _ptr(traj), _ptr(acc), N.OE_ASYNC)
+            if len(spans) == 1:
+                self.ctx.band_hist(w, _ptr(traj), _ptr(acc), _ptr(hist), N.OE_ASYNC)
+        if len(spans) > 1:
+            for a, b in spans:
+                w, traj = run(a, b, False)
+                self.ctx.band_hist(w, _ptr(traj), _ptr(acc), _ptr(hist), N.OE_ASYNC)
+        self.ctx.band_quantiles(_ptr(acc), _ptr(hist), q, _ptr(out), N.OE_ASYNC)
+        torch.cuda.synchronize(self.dev)
+        res = band_summary(acc.cpu().numpy())
+        res["q"] = out.cpu().numpy()
+        res["status_or"] = int(st_or.item())
+        res["n_status"] = int(st_n.item())
+        return res
 
     def last_kernel_ms(self) -> float:
         return self.ctx.last_kernel_ms()

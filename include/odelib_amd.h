@@ -22,6 +22,9 @@
  *   oe_band_*        <- plot_uncertainty (Framework.py:734-740), which overlays 100 random
  *                       posterior rows: here every row is summarised (count, log-space
  *                       moments, min, max, quantiles per grid time and output column).
+ *   oe_diag_run      <- nothing in the reference: split R-hat, autocorrelations, effective
+ *                       sample size and Monte-Carlo standard error of the kept draws, where
+ *                       oe_mh_run left them (the reference offers rawstats' median and sd).
  *   oe_allgather_samples <- the pd.concat of the per-process chain posteriors
  *                       (Framework.py:1035-1038) after Pool.starmap (:779-780):
  *                       one RCCL all-gather of the ranks' sample blocks.
@@ -363,6 +366,58 @@ int oe_band_hist(oe_ctx* ctx, int64_t n_walkers, const double* traj, const doubl
 /* out [n_q][T][n_cols] */
 int oe_band_quantiles(oe_ctx* ctx, const double* acc, const uint32_t* hist, int32_t n_q, const double* q,
                       double* out, uint32_t flags);
+
+/* ---- MCMC convergence diagnostics: split R-hat, autocorrelations, ESS, MCSE -----------------
+ * (Added under ABI 7: a new struct and a new function, nothing existing changes, so
+ * OE_ABI_VERSION stays 7 and a caller built against the earlier header keeps working.)
+ * Did the chains converge, and how many independent draws is the run worth?  Computed from the
+ * kept draws where oe_mh_run left them, in the chains' own layout.
+ *   x[k][w] = g(samples[k][row][w]) for a selected row, g the identity or the natural log;
+ *   n = K div 2; split chain (w, 0) is draws 0..n-1, (w, 1) is draws K-n..K-1 (an odd K drops
+ *   the middle draw).  Chain w is valid for the row iff all K transformed values are finite
+ *   (the log of a value <= 0 is not); M = 2 (valid chains); invalid chains take no part.
+ *   Per split chain j: mean m_j, c_{j,k} = x - m_j, biased autocovariance
+ *   a_j(t) = (1/n) sum_{k=0}^{n-1-t} c_{j,k} c_{j,k+t}, s_j^2 = n/(n-1) a_j(0).
+ *   Across chains: Wbar = mean_j s_j^2, B = n/(M-1) sum_j (m_j - mbar)^2,
+ *   var+ = (n-1)/n Wbar + B/n, rhat = sqrt(var+/Wbar), rho_0 = 1,
+ *   rho_t = 1 - (Wbar - abar(t))/var+ with abar(t) = mean_j a_j(t), 1 <= t <= max_lag.
+ *   Geyer's initial monotone sequence: P_k = rho_{2k} + rho_{2k+1}, k = 0, 1, ... while
+ *   2k+1 <= max_lag.  At the first P_k < 0 the walk stops: that pair is not included,
+ *   stop_lag = 2k, truncated = 0.  Otherwise P'_k = min(P_k, P'_{k-1}) is added.  If the pairs
+ *   run out: truncated = 1, stop_lag = 2 (pairs used).  tau = max(-1 + 2 sum P'_k, 1/log10(M n)),
+ *   ess = M n / tau, mcse = sqrt(var+/ess).
+ *   Degenerate rows.  M = 0: n_chains = 0, every other field NaN.  Wbar equal to 0 or not finite
+ *   (a static parameter, chains that never moved): rhat, tau, ess, mcse, stop_lag, truncated
+ *   and the row's rho are NaN; mean, W, B, var+ and n_chains are reported.
+ * Outputs (device):
+ *   summary     [n_sel][12] doubles: n_chains, n, grand mean, Wbar, B, var+, rhat, tau, ess, mcse,
+ *               stop_lag, truncated;
+ *   rho         [n_sel][max_lag+1] or NULL: rho_t for the lags evaluated, 0..stop_lag+1 when the
+ *               walk stopped, 0..max_lag when it was truncated; NaN past them;
+ *   chain_stats [n_sel][2][2][W] or NULL: per row and half, m_j then s_j^2; NaN for an invalid chain.
+ * Sums over a chain's draws are centred (a shifted mean, then deviations from it), sums across
+ * chains run in a fixed order without floating-point atomics: the same bits run to run.  The
+ * across-chain parts (M, mbar, sum (m_j - mbar)^2, sum s_j^2, sum a_j(t)) are mergeable across
+ * ranks by a Chan merge and plain sums.
+ * Needs a context, no oe_problem_set.  Launched on the context's stream without a host
+ * synchronisation between the first launch and the last; synchronous on return unless OE_ASYNC.
+ * The context keeps a device scratch of about 16 n_sel W bytes.
+ * OE_ERR_ARG: OE_HOST_PTRS, a null samples / summary / rows, K < 8, n_walkers outside 1..2^29,
+ * n_sel outside 1..64, a row outside 0..R_tot-1, max_lag outside 0..n-1 (0 means n-1). */
+typedef struct {
+  const double* samples; /* [K][R_tot][W] device: element (k, row, w) at (k*R_tot + row)*W + w */
+  int32_t K;             /* kept draws per chain */
+  int32_t R_tot;         /* rows per draw (oe_mh_run: P + 5) */
+  int64_t n_walkers;     /* W chains */
+  int32_t n_sel;         /* selected rows */
+  const int32_t* rows;   /* [n_sel] host */
+  const uint8_t* log_rows; /* [n_sel] host: 1 = diagnose the natural log of the row; NULL: none */
+  int32_t max_lag;       /* 1..n-1, 0 = n-1 */
+  double* summary;       /* [n_sel][12] device */
+  double* rho;           /* [n_sel][max_lag+1] device, or NULL */
+  double* chain_stats;   /* [n_sel][2][2][W] device, or NULL */
+} oe_diag_args;
+int oe_diag_run(oe_ctx* ctx, const oe_diag_args* args, uint32_t flags);
 
 /* Device time (ms) of the kernel launches of the last oe_integrate / oe_mh_run,
  * from HIP events recorded on the context's stream around them (waits for them). */

@@ -156,6 +156,24 @@ def band_inputs(pnames, snames, inits, posteriors):
     return theta, y0
 
 
+def diag_inputs(posterior, pnames):
+    """The posterior DataFrame ``MCMC`` returns -> the [K][P+1][W] array ``Engine.diagnose``
+    takes: the ``pnames`` columns and ``chi``, one chain per value of ``chain#`` (in increasing
+    order), each chain's rows in order of ``iteration``.  Chains of unequal length or of fewer
+    than 8 rows raise ValueError; a missing column raises KeyError."""
+    cols = list(pnames) + ["chi"]
+    frame = posterior[cols + ["chain#", "iteration"]]
+    frame = frame.sort_values(["chain#", "iteration"], kind="stable")
+    counts = frame.groupby("chain#", sort=True).size().to_numpy()
+    if len(counts) == 0 or (counts != counts[0]).any():
+        raise ValueError("the chains of the posterior must have the same number of rows")
+    W, K = len(counts), int(counts[0])
+    if K < 8:
+        raise ValueError("convergence diagnostics need at least 8 rows per chain")
+    block = frame[cols].to_numpy(dtype=float).reshape(W, K, len(cols))
+    return np.ascontiguousarray(np.transpose(block, (1, 2, 0)))
+
+
 class ModelFramework:
     """ODE model + data + priors (Framework.py:166-1166), computed on MI355X."""
 
@@ -501,6 +519,32 @@ class ModelFramework:
         ax.fill_between(b["time"], b[f"q{lo:g}"], b[f"q{hi:g}"], color=str(0.8), zorder=1)
         ax.plot(b["time"], b["q0.5"], c=str(0.3), lw=1, zorder=2)
         return band
+
+    def convergence(self, posterior, max_lag=None):
+        """Did the chains converge, and how many independent draws is the posterior worth?
+        Split R-hat, effective sample size and Monte-Carlo standard error per parameter and for
+        chi, computed on the device (``Engine.diagnose``).  ``posterior``: the
+        DataFrame ``MCMC`` returns, or the dict ``Samplers.batched_metropolis_hastings(...,
+        return_device=True)`` returns, whose draws are read where they lie on the device.
+        Parameters are diagnosed in log space, as ``rawstats`` works; chi as it is.  Returns a
+        DataFrame indexed by ``get_pnames() + ['chi']`` with the columns rhat, ess, mcse, tau,
+        mean, sd (the square root of the pooled variance estimate), n_chains, stop_lag (the lag
+        at which Geyer's sequence stopped) and truncated (1: it ran out of lags first).  A
+        parameter that never moved (``static_parameters``) has NaN rhat, ess, mcse and tau."""
+        pnames = self.get_pnames()
+        P = len(pnames)
+        if isinstance(posterior, pd.DataFrame):
+            samples = diag_inputs(posterior, pnames)
+        else:
+            samples = posterior["samples"]
+            if samples.dim() != 3 or samples.shape[1] < P + 1:
+                raise ValueError(f"samples must be [K][{P + 5}][W]")
+        res = self.engine().diagnose(samples, rows=list(range(P + 1)), log_rows=[1] * P + [0], max_lag=max_lag)
+        out = pd.DataFrame({"rhat": res["rhat"], "ess": res["ess"], "mcse": res["mcse"], "tau": res["tau"],
+                            "mean": res["mean"], "sd": np.sqrt(res["var_plus"]), "n_chains": res["n_chains"],
+                            "stop_lag": res["stop_lag"], "truncated": res["truncated"]},
+                           index=pnames + ["chi"])
+        return out
 
     # ------------------------------------------------------------------ LHS survey
     def _lhs_samples(self, samples=100, **kwargs):

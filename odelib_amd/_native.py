@@ -62,6 +62,7 @@ EXPORTED = (
     "oe_band_moments",
     "oe_band_hist",
     "oe_band_quantiles",
+    "oe_diag_run",
 )
 
 
@@ -121,6 +122,26 @@ class OEMHArgs(C.Structure):
         ("it_start", C.c_int32),
         ("speculate", C.c_int32),
     ]
+
+
+class OEDiagArgs(C.Structure):
+    _fields_ = [
+        ("samples", C.c_void_p),
+        ("K", C.c_int32),
+        ("R_tot", C.c_int32),
+        ("n_walkers", C.c_int64),
+        ("n_sel", C.c_int32),
+        ("rows", C.c_void_p),
+        ("log_rows", C.c_void_p),
+        ("max_lag", C.c_int32),
+        ("summary", C.c_void_p),
+        ("rho", C.c_void_p),
+        ("chain_stats", C.c_void_p),
+    ]
+
+
+# the fields of a row of oe_diag_run's summary, in order
+DIAG_FIELDS = ("n_chains", "n", "mean", "W", "B", "var_plus", "rhat", "tau", "ess", "mcse", "stop_lag", "truncated")
 
 
 _lib = None
@@ -204,6 +225,8 @@ def load_library(path: str | None = None):
         lib.oe_band_hist.argtypes = [vp, i64, vp, vp, vp, u32]
         lib.oe_band_quantiles.restype = C.c_int
         lib.oe_band_quantiles.argtypes = [vp, vp, vp, i32, vp, vp, u32]
+        lib.oe_diag_run.restype = C.c_int
+        lib.oe_diag_run.argtypes = [vp, C.POINTER(OEDiagArgs), u32]
         if lib.oe_abi_version() != OE_ABI_VERSION:
             raise NativeUnavailable("libodelib_amd.so ABI version mismatch; rebuild it")
         if path is None:
@@ -296,6 +319,19 @@ class Context:
         qa = np.ascontiguousarray(np.asarray(q, dtype=np.float64))
         self._check(self.lib.oe_band_quantiles(self._h, acc, hist, len(qa), C.c_void_p(qa.ctypes.data), out,
                                                int(flags)), "oe_band_quantiles")
+
+    def diag_run(self, samples, K, R_tot, n_walkers, rows, log_rows, max_lag, summary, rho=None, chain_stats=None,
+                 flags=0):
+        """``oe_diag_run``: ``rows`` / ``log_rows`` host sequences, the rest device pointers."""
+        import numpy as np
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32))
+        lg = np.ascontiguousarray(np.asarray(log_rows if log_rows is not None else np.zeros(len(r)), dtype=np.uint8))
+        if len(lg) != len(r):
+            raise ValueError("log_rows must have one entry per selected row")
+        a = OEDiagArgs(samples=samples, K=int(K), R_tot=int(R_tot), n_walkers=int(n_walkers), n_sel=len(r),
+                       rows=r.ctypes.data, log_rows=lg.ctypes.data, max_lag=int(max_lag), summary=summary, rho=rho,
+                       chain_stats=chain_stats)
+        self._check(self.lib.oe_diag_run(self._h, C.byref(a), int(flags)), "oe_diag_run")
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "band.cuh"
+#include "diag.cuh"
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
 
@@ -22,3 +23,8 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_band_moments(const oe::BandA
 __global__ void __launch_bounds__(256) k_band_merge(const oe::BandArgs a);
 __global__ void __launch_bounds__(oe::kBandBlock) k_band_hist(const oe::BandArgs a);
 __global__ void __launch_bounds__(256) k_band_quantiles(const oe::BandQArgs a);
+// MCMC convergence diagnostics (diag.cuh): split R-hat, autocorrelations, ESS of the kept draws
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_moments(const oe::DiagArgs a);
+__global__ void __launch_bounds__(64) k_diag_merge(const oe::DiagArgs a);
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_acov(const oe::DiagArgs a);
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_eval(const oe::DiagArgs a);

@@ -58,7 +58,9 @@ using plan::kMaxWalkers;
 // launch_plan.h restates the device headers' constants (it includes none of them)
 static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRegS &&
                   plan::kHandBdfWaves == kHandBdfWaves && plan::kResolveLdsDepth == kResolveLdsDepth &&
-                  plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile,
+                  plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile &&
+                  plan::kDiagBlock == kDiagBlock && plan::kDiagLB == kDiagLB && plan::kDiagPart == kDiagPart &&
+                  plan::kDiagState == kDiagState,
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -118,8 +120,9 @@ struct oe_ctx {
   DevBuf hq;        // the hand-over queue, below
   DevBuf band_part;  // k_band_moments' partials, one cell per workgroup and column
   DevBuf band_tab;   // the band's column masks [64] uint64, then its quantiles [64] doubles
-  std::array<DevBuf*, 9> bufs() {
-    return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab};
+  DevBuf diag;       // oe_diag_run's scratch (launch_plan.h DiagPlan)
+  std::array<DevBuf*, 10> bufs() {
+    return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag};
   }
   // posterior bands (oe_band_begin .. oe_band_quantiles); the tables' host copies live here so
   // an asynchronous upload never reads the caller's arrays after the call
@@ -1152,6 +1155,63 @@ int oe_band_quantiles(oe_ctx* c, const double* acc, const uint32_t* hist, int32_
   const int64_t n = (int64_t)a.T * a.n_cols * n_q;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_band_quantiles), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), c->stream, a));
+  return band_finish(c, flags);
+}
+
+// ---- MCMC convergence diagnostics (diag.cuh) --------------------------
+int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!g) return fail(c, OE_ERR_ARG, "oe_diag_run: args is null");
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_diag_run: device pointers only");
+  if (!g->samples || !g->summary || !g->rows)
+    return fail(c, OE_ERR_ARG, "oe_diag_run: samples, summary and rows are required");
+  if (g->K < 8) return fail(c, OE_ERR_ARG, "oe_diag_run: K must be at least 8 kept draws");
+  const int64_t W = g->n_walkers;
+  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_diag_run: n_walkers must be in [1, 2^29]");
+  if (g->n_sel < 1 || g->n_sel > kDiagMaxRows) return fail(c, OE_ERR_ARG, "oe_diag_run: n_sel must be in [1, 64]");
+  if (g->R_tot < 1) return fail(c, OE_ERR_ARG, "oe_diag_run: R_tot must be positive");
+  for (int r = 0; r < g->n_sel; ++r)
+    if (g->rows[r] < 0 || g->rows[r] >= g->R_tot)
+      return fail(c, OE_ERR_ARG, "oe_diag_run: a selected row is outside [0, R_tot)");
+  if (g->max_lag < 0 || g->max_lag > g->K / 2 - 1)
+    return fail(c, OE_ERR_ARG, "oe_diag_run: max_lag must be in [1, K/2 - 1], or 0 for K/2 - 1");
+  OE_DEVICE_GUARD(c);
+  const plan::DiagPlan pl = plan::plan_diag(g->K, W, g->n_sel, g->max_lag);
+  const int rc = c->diag.reserve(c, pl.bytes);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->diag.p);
+  DiagArgs a{};
+  a.samples = g->samples;
+  a.summary = g->summary;
+  a.rho = g->rho;
+  a.chain_stats = g->chain_stats;
+  a.cmean = reinterpret_cast<double*>(base + pl.off_cmean);
+  a.mpart = reinterpret_cast<double*>(base + pl.off_mpart);
+  a.apart = reinterpret_cast<double*>(base + pl.off_apart);
+  a.acov_sum = reinterpret_cast<double*>(base + pl.off_acov);
+  a.state = reinterpret_cast<double*>(base + pl.off_state);
+  a.done = reinterpret_cast<int32_t*>(base + pl.off_done);
+  a.W = W;
+  a.stride = (int64_t)g->R_tot * W;
+  a.K = g->K;
+  a.n = pl.n;
+  a.n_sel = g->n_sel;
+  a.max_lag = pl.max_lag;
+  a.bpr = pl.blocks_per_row;
+  for (int r = 0; r < g->n_sel; ++r) {
+    a.rows[r] = g->rows[r];
+    if (g->log_rows && g->log_rows[r]) a.log_mask |= 1ull << r;
+  }
+  // everything is enqueued up front: a row whose walk has stopped marks itself done on the
+  // device, and the later lag blocks return at once for it
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_diag_moments), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_diag_merge), dim3(pl.row_grid), dim3(64), c->stream, a));
+  for (int b = 0; b < pl.lag_blocks; ++b) {
+    a.t0 = plan::plan_diag_first_lag(b);
+    OE_HIP(c, launch(kernel_of(k_diag_acov), dim3(pl.grid), dim3(pl.block), c->stream, a));
+    OE_HIP(c, launch(kernel_of(k_diag_eval), dim3(pl.row_grid), dim3(kDiagBlock), c->stream, a));
+  }
   return band_finish(c, flags);
 }
 

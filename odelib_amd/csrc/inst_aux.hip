@@ -1,6 +1,6 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
 // (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
-// posterior band reductions.
+// posterior band reductions, the convergence diagnostics.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -219,3 +219,9 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_band_moments(const oe::BandA
 __global__ void __launch_bounds__(256) k_band_merge(const oe::BandArgs a) { oe::band_merge(a); }
 __global__ void __launch_bounds__(oe::kBandBlock) k_band_hist(const oe::BandArgs a) { oe::band_hist(a); }
 __global__ void __launch_bounds__(256) k_band_quantiles(const oe::BandQArgs a) { oe::band_quantiles(a); }
+
+// MCMC convergence diagnostics of the kept draws (diag.cuh)
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_moments(const oe::DiagArgs a) { oe::diag_moments(a); }
+__global__ void __launch_bounds__(64) k_diag_merge(const oe::DiagArgs a) { oe::diag_merge(a); }
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_acov(const oe::DiagArgs a) { oe::diag_acov(a); }
+__global__ void __launch_bounds__(oe::kDiagBlock) k_diag_eval(const oe::DiagArgs a) { oe::diag_eval(a); }

@@ -1,7 +1,8 @@
-// launch_plan.h — what oe_integrate, oe_mh_run and the oe_band_* passes launch, decided by
-// pure functions: numbers in, a plan out (kernel, grids, half waves, XCD runs, the hand-over
-// queue's placement, speculation depth, chunk, buffer sizes).  No HIP here, so
-// tests/sanitize/plan_driver.cpp and band_plan_driver.cpp check the arithmetic on the CPU;
+// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes and oe_diag_run launch,
+// decided by pure functions: numbers in, a plan out (kernel, grids, half waves, XCD runs, the
+// hand-over queue's placement, speculation depth, chunk, lag blocks, buffer sizes).  No HIP here,
+// so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp and diag_plan_driver.cpp check the
+// arithmetic on the CPU;
 // capi.hip reserves, fills the arguments and launches.
 #pragma once
 #include <algorithm>
@@ -339,6 +340,55 @@ inline int64_t plan_band_chunk(int T, int S, int64_t W_total, int64_t budget_byt
   const int64_t fit = budget_bytes / per_walker / 256 * 256;
   const int64_t all = (W_total + 255) / 256 * 256;
   return std::max<int64_t>(256, std::min(fit, all));
+}
+
+// ---- oe_diag_run --------------------------------------------------------------------
+constexpr int kDiagBlock = 256;  // chains per workgroup (one lane per chain)
+constexpr int kDiagLB = 16;      // lags per pass of k_diag_acov
+constexpr int kDiagPart = 4;     // doubles per moments partial
+constexpr int kDiagState = 4;    // doubles of the walk's state per row
+
+struct DiagPlan {
+  int32_t n = 0;                           // draws per split chain, K div 2
+  int32_t max_lag = 0;                     // resolved: 0 means n - 1
+  unsigned grid = 0, block = kDiagBlock;   // k_diag_moments / k_diag_acov: n_sel * blocks_per_row
+  int32_t blocks_per_row = 0;              // workgroup (r, j): chains [256 j, min(W, 256 (j + 1)))
+  unsigned row_grid = 0;                   // k_diag_merge (64 lanes) / k_diag_eval (256): one per row
+  int32_t lag_blocks = 0;                  // (k_diag_acov, k_diag_eval) pairs: lags 1..max_lag
+  // the scratch, one buffer: byte offsets of its parts (each a multiple of 256) and the total
+  size_t off_cmean = 0;   // [n_sel][2][W] doubles
+  size_t off_mpart = 0;   // [n_sel][blocks_per_row][kDiagPart] doubles
+  size_t off_apart = 0;   // [n_sel][blocks_per_row][kDiagLB] doubles
+  size_t off_acov = 0;    // [n_sel][max_lag + 1] doubles
+  size_t off_state = 0;   // [n_sel][kDiagState] doubles
+  size_t off_done = 0;    // [n_sel] int32
+  size_t bytes = 0;
+};
+
+// the first lag of lag block b: block b covers lags first .. min(first + kDiagLB - 1, max_lag)
+inline int32_t plan_diag_first_lag(int32_t b) { return 1 + b * kDiagLB; }
+
+// K >= 8 kept draws, 1 <= W <= 2^29 chains, 1 <= n_sel <= 64 rows, max_lag in 0..K/2 - 1
+inline DiagPlan plan_diag(int32_t K, int64_t W, int32_t n_sel, int32_t max_lag) {
+  DiagPlan p;
+  p.n = K / 2;
+  p.max_lag = max_lag > 0 ? max_lag : p.n - 1;
+  p.blocks_per_row = (int32_t)((W + kDiagBlock - 1) / kDiagBlock);
+  p.grid = (unsigned)((int64_t)n_sel * p.blocks_per_row);
+  p.row_grid = (unsigned)n_sel;
+  p.lag_blocks = (p.max_lag + kDiagLB - 1) / kDiagLB;
+  auto part = [&p](size_t& off, size_t bytes) {
+    off = p.bytes;
+    p.bytes += (bytes + 255) / 256 * 256;
+  };
+  const size_t rows = (size_t)n_sel, bpr = (size_t)p.blocks_per_row;
+  part(p.off_cmean, sizeof(double) * rows * 2 * (size_t)W);
+  part(p.off_mpart, sizeof(double) * rows * bpr * kDiagPart);
+  part(p.off_apart, sizeof(double) * rows * bpr * kDiagLB);
+  part(p.off_acov, sizeof(double) * rows * (size_t)(p.max_lag + 1));
+  part(p.off_state, sizeof(double) * rows * kDiagState);
+  part(p.off_done, sizeof(int32_t) * rows);
+  return p;
 }
 
 }  // namespace plan

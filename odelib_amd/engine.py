@@ -390,6 +390,49 @@ class Engine:
         res["n_status"] = int(st_n.item())
         return res
 
+    # -- MCMC convergence diagnostics -------------------------------------------------------------
+    def diagnose(self, samples, rows=None, log_rows=None, max_lag=None, rho=False, chain_stats=False):
+        """Split R-hat, effective sample size and Monte-Carlo standard error of kept draws
+        (the estimator is stated at ``oe_diag_run`` in include/odelib_amd.h).
+
+        ``samples``: a device tensor or host array [K][R_tot][W] (``mh_run``'s ``samples``: a
+        device tensor is read where it lies).  ``rows``: the rows to diagnose (default: all);
+        ``log_rows``: per selected row, whether its natural log is diagnosed (default: none).
+        ``max_lag``: the largest autocorrelation lag, 1..K//2 - 1 (default: K//2 - 1).
+        Returns a dict of host arrays [n_sel] named as the summary's fields (``n_chains``,
+        ``n``, ``mean``, ``W``, ``B``, ``var_plus``, ``rhat``, ``tau``, ``ess``, ``mcse``,
+        ``stop_lag``, ``truncated``), plus ``rho`` [n_sel][max_lag + 1] and ``chain_stats``
+        [n_sel][2][2][W] (per half: mean, then variance) when asked."""
+        torch = self.torch
+        if isinstance(samples, torch.Tensor):
+            s = samples.to(device=self.dev, dtype=torch.float64).contiguous()
+        else:
+            s = torch.as_tensor(np.ascontiguousarray(np.asarray(samples, dtype=np.float64)), device=self.dev)
+        if s.dim() != 3:
+            raise ValueError("samples must be [K][R_tot][W]")
+        K, R_tot, W = (int(v) for v in s.shape)
+        sel = np.arange(R_tot, dtype=np.int32) if rows is None else np.asarray(rows, dtype=np.int32).reshape(-1)
+        lg = np.zeros(len(sel), dtype=np.uint8) if log_rows is None else np.asarray(log_rows).astype(np.uint8).reshape(-1)
+        if len(lg) != len(sel):
+            raise ValueError("log_rows must have one entry per selected row")
+        lag = 0 if max_lag is None else int(max_lag)
+        if max_lag is not None and lag < 1:
+            raise ValueError("max_lag must be at least 1")
+        n_lag = (lag if lag else K // 2 - 1) + 1
+        summary = torch.empty((len(sel), len(N.DIAG_FIELDS)), dtype=torch.float64, device=self.dev)
+        rho_t = torch.empty((len(sel), max(n_lag, 1)), dtype=torch.float64, device=self.dev) if rho else None
+        cs_t = torch.empty((len(sel), 2, 2, W), dtype=torch.float64, device=self.dev) if chain_stats else None
+        self._sync_stream()
+        self.ctx.diag_run(_ptr(s), K, R_tot, W, sel, lg, lag, _ptr(summary), _ptr(rho_t), _ptr(cs_t), N.OE_ASYNC)
+        torch.cuda.synchronize(self.dev)
+        out = summary.cpu().numpy()
+        res = {name: out[:, k].copy() for k, name in enumerate(N.DIAG_FIELDS)}
+        if rho:
+            res["rho"] = rho_t.cpu().numpy()
+        if chain_stats:
+            res["chain_stats"] = cs_t.cpu().numpy()
+        return res
+
     def last_kernel_ms(self) -> float:
         return self.ctx.last_kernel_ms()
 

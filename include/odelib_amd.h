@@ -419,6 +419,48 @@ typedef struct {
 } oe_diag_args;
 int oe_diag_run(oe_ctx* ctx, const oe_diag_args* args, uint32_t flags);
 
+/* ---- posterior-wide model comparison: WAIC and its pointwise terms ----------------------------
+ * (Added under ABI 7: three new functions, nothing existing changes, OE_ABI_VERSION stays 7.)
+ * Which model does the whole posterior prefer, and by how much relative to the uncertainty?
+ * The posterior's rows are streamed through oe_integrate in chunks, as for the bands; each
+ * chunk's trajectory traj [T][S][W] is folded, observation by observation, into one cell of
+ * five doubles.  For observation o of the problem set in the context and walker w:
+ *   C = sum of the states in obs_mask[o] at grid index obs_tidx[o], in increasing state order;
+ *   d = obs_log[o] - log C; term = (d d) / (2 obs_logsigma[o]^2), the element oe_integrate's chi
+ *   sums; the element is valid iff term is finite (chi's rule); e = -term.
+ *   The pointwise log-likelihood is ll = e + c_o with the Gaussian normaliser
+ *   c_o = -(log obs_logsigma[o] + log(2 pi) / 2).
+ *   acc [n_obs][5] doubles over the valid elements of every chunk folded so far: n, mean of e,
+ *   M2 of e (Welford per lane, Chan merges), a = max e, s = sum exp(e - a) (an online
+ *   log-sum-exp: one pass whatever the number of chunks).  The cells are kept in the order of
+ *   the context's sorted observation records; they are opaque between the three calls.
+ * oe_waic_finish writes, in the order of the caller's oe_problem arrays,
+ *   pointwise [n_obs][6]: n, lppd_o = a + log(s / n) + c_o (the log of the mean likelihood),
+ *       p_waic_o = M2 / (n - 1) (the sample variance of ll), elpd_o = lppd_o - p_waic_o,
+ *       mean_ll_o = mean e + c_o, max_ll_o = a + c_o.  n = 0: every field after n is NaN;
+ *       n = 1: p_waic_o and elpd_o are NaN.
+ *   summary [8]: n_obs_used (observations with n >= 2), and over those, added in increasing
+ *       observation order, lppd, p_waic, elpd_waic; waic = -2 elpd_waic;
+ *       se_elpd = sqrt(m var_{m-1}(elpd_o)), m = n_obs_used, a two-pass variance (NaN if m < 2);
+ *       n_high_var, the observations with p_waic_o > 0.4 (the usual reliability flag of WAIC,
+ *       Vehtari, Gelman and Gabry 2017); n_rows_min, the smallest n.
+ * terms (oe_waic_accum, optional): [n_obs][terms_ld] doubles in the caller's observation order;
+ *   the chunk's term of walker w goes to terms[o][w_offset + w], NaN where it is not valid.
+ * Merges run in a fixed order (lane, wave, workgroup, the workgroups' partials in block order)
+ * without floating-point atomics: every output is the same bits run to run for one chunking; n
+ * and terms are the same bits for any chunking, the rest agrees across chunkings to rounding.
+ * Order of calls: oe_waic_begin; oe_waic_accum for every chunk; oe_waic_finish (which leaves acc
+ * as it is: more chunks may follow).
+ * Device pointers only; launched on the context's stream; synchronous on return unless OE_ASYNC
+ * (oe_waic_begin: always synchronous).
+ * OE_ERR_STATE without a context, before oe_problem_set, or before oe_waic_begin (oe_problem_set
+ * ends a pass); OE_ERR_ARG: a problem with n_obs == 0, a null acc / traj / pointwise / summary,
+ * n_walkers < 1, OE_HOST_PTRS, or terms with w_offset < 0 or w_offset + n_walkers > terms_ld. */
+int oe_waic_begin(oe_ctx* ctx, double* acc);
+int oe_waic_accum(oe_ctx* ctx, int64_t n_walkers, const double* traj, double* acc, double* terms, int64_t terms_ld,
+                  int64_t w_offset, uint32_t flags);
+int oe_waic_finish(oe_ctx* ctx, const double* acc, double* pointwise, double* summary, uint32_t flags);
+
 /* Device time (ms) of the kernel launches of the last oe_integrate / oe_mh_run,
  * from HIP events recorded on the context's stream around them (waits for them). */
 int oe_last_kernel_ms(oe_ctx* ctx, double* ms);

@@ -28,6 +28,7 @@ summation and fails on models with state summations, Framework.py:34-35);
 from __future__ import annotations
 
 import itertools
+import math
 import random
 import warnings
 
@@ -172,6 +173,52 @@ def diag_inputs(posterior, pnames):
         raise ValueError("convergence diagnostics need at least 8 rows per chain")
     block = frame[cols].to_numpy(dtype=float).reshape(W, K, len(cols))
     return np.ascontiguousarray(np.transpose(block, (1, 2, 0)))
+
+
+COMPARE_COLUMNS = ("elpd_waic", "se_elpd", "p_waic", "waic", "dic", "d_elpd", "se_d")
+
+
+def compare(results):
+    """Rank models by WAIC.  ``results``: a dict mapping a name to what ``ModelFramework.waic``
+    returned for that model (with its ``pointwise`` frame) on one data set.  Returns a DataFrame
+    indexed by name, sorted by ``elpd_waic`` with the best (largest) first, with the columns
+    elpd_waic, se_elpd, p_waic, waic, dic, d_elpd (the model's elpd_waic minus the best's: 0 for
+    the best, negative below it) and se_d = sqrt(m var(elpd_o - elpd_o of the best)), the
+    variance with m - 1 in the denominator over the m observations both models used: how far
+    d_elpd lies from 0 in units of its own uncertainty is the comparison.  The models must
+    have been scored on the same observations: ValueError if the number of observations, their
+    times or their organisms differ."""
+    if not results:
+        raise ValueError("compare needs at least one result")
+    names = list(results)
+    frames = {}
+    for name in names:
+        pw = results[name].get("pointwise")
+        if pw is None:
+            raise ValueError(f"result {name!r} has no pointwise frame (waic(..., pointwise=True))")
+        frames[name] = pw
+    first = frames[names[0]]
+    for name in names[1:]:
+        pw = frames[name]
+        if len(pw) != len(first):
+            raise ValueError(f"{name!r} was scored on {len(pw)} observations, {names[0]!r} on {len(first)}")
+        if not np.array_equal(pw["time"].to_numpy(), first["time"].to_numpy()) or \
+                not np.array_equal(pw["organism"].to_numpy(), first["organism"].to_numpy()):
+            raise ValueError(f"{name!r} and {names[0]!r} were scored on different observations")
+    table = pd.DataFrame({c: [results[n].get(c, np.nan) for n in names] for c in COMPARE_COLUMNS[:5]},
+                         index=names, dtype=float)
+    table = table.sort_values("elpd_waic", ascending=False, kind="stable", na_position="last")
+    best = table.index[0]
+    e_best = frames[best]["elpd"].to_numpy(dtype=float)
+    d_elpd, se_d = [], []
+    for name in table.index:
+        d = frames[name]["elpd"].to_numpy(dtype=float) - e_best
+        d = d[np.isfinite(d)]
+        d_elpd.append(table.loc[name, "elpd_waic"] - table.loc[best, "elpd_waic"])
+        se_d.append(float(np.sqrt(len(d) * np.var(d, ddof=1))) if len(d) > 1 else np.nan)
+    table["d_elpd"] = d_elpd
+    table["se_d"] = se_d
+    return table[list(COMPARE_COLUMNS)]
 
 
 class ModelFramework:
@@ -544,6 +591,73 @@ class ModelFramework:
                             "mean": res["mean"], "sd": np.sqrt(res["var_plus"]), "n_chains": res["n_chains"],
                             "stop_lag": res["stop_lag"], "truncated": res["truncated"]},
                            index=pnames + ["chi"])
+        return out
+
+    def _obs_frame(self):
+        """The observations the fit problem holds as rows of ``self.df``, in its order: a frame
+        of organism, time and abundance, and for each row the observation's index in the fit
+        problem (``fit_problem``: output column after output column, each organism's rows in
+        the table's order).  Rows of organisms that are no output column are not observations."""
+        _, cols, _ = self._obs_layout()
+        start, at = {}, 0
+        for sname, _ in cols:
+            start[sname] = at
+            at += len(self._pred_tindex[sname])
+        seen = dict.fromkeys(start, 0)
+        keep, index = [], []
+        for r, organism in enumerate(self.df.index):
+            if organism in start:
+                keep.append(r)
+                index.append(start[organism] + seen[organism])
+                seen[organism] += 1
+        rows = self.df.iloc[keep]
+        frame = pd.DataFrame({"organism": rows.index.to_numpy(), "time": rows["time"].to_numpy(),
+                              "abundance": rows["abundance"].to_numpy()})
+        return frame, np.asarray(index, dtype=np.int64)
+
+    def waic(self, posteriors, chunk=None, pointwise=True):
+        """Which model does the whole posterior prefer?  WAIC (the widely applicable information
+        criterion) and DIC of this model over every row of ``posteriors`` (DataFrame with the
+        parameter columns, or [W][P] array; a '<state>0' parameter sets that state's initial
+        value per row), computed on the device (``Engine.waic``): the rows are
+        integrated in chunks and every observation's log-likelihood is reduced across them
+        there.  Returns a dict: ``elpd_waic`` (the expected log pointwise predictive density:
+        larger is better), ``se_elpd``, ``p_waic`` (the effective number of parameters),
+        ``waic`` = -2 elpd_waic, ``lppd``, ``n_obs_used``, ``n_high_var`` (observations whose
+        posterior variance of the log-likelihood exceeds 0.4: WAIC is unreliable when there are
+        many), ``n_rows_min``, ``n_rows``, ``status_or``, ``n_status``; ``dbar`` (the posterior
+        mean deviance), ``p_d`` = dbar - D(theta_hat) with theta_hat the posterior mean in log
+        space (as ``rawstats`` works) and ``dic`` = dbar + p_d, all three NaN unless every row
+        has a finite term at every observation, every parameter is positive and chi(theta_hat)
+        is finite; and, unless ``pointwise=False``, ``pointwise``: one row per observation in
+        ``self.df`` order with organism, time, abundance, n, lppd, p_waic, elpd, mean_ll, max_ll.
+        ``compare`` ranks several models' results."""
+        if self.df is None:
+            raise ValueError("waic needs a model with data")
+        theta, y0 = band_inputs(self._pnames, self._snames, self.get_inits(), posteriors)
+        eng = self.engine()
+        res = eng.waic(y0, theta, chunk=chunk)
+        W = theta.shape[1]
+        out = dict(res["summary"])
+        out.update(n_rows=W, status_or=res["status_or"], n_status=res["n_status"])
+        # DIC: the mean deviance against the deviance at the posterior mean (log space)
+        sigma = np.asarray(eng.problem.obs_logsigma, dtype=float)
+        c_sum = math.fsum(-(np.log(sigma) + 0.5 * np.log(2.0 * np.pi)))
+        dbar = p_d = dic = np.nan
+        if (res["n"] == W).all() and (theta > 0).all():
+            hat = np.exp(np.mean(np.log(theta), axis=1))
+            th_hat, y0_hat = band_inputs(self._pnames, self._snames, self.get_inits(), hat[None, :])
+            chi = float(eng.integrate(y0_hat, th_hat, trajectory=False)["chi"].cpu().numpy()[0])
+            if np.isfinite(chi):
+                dbar = -2.0 * math.fsum(res["mean_ll"])
+                p_d = dbar - (2.0 * chi - 2.0 * c_sum)
+                dic = dbar + p_d
+        out.update(dbar=dbar, p_d=p_d, dic=dic)
+        if pointwise:
+            frame, index = self._obs_frame()
+            for k in ("n", "lppd", "p_waic", "elpd", "mean_ll", "max_ll"):
+                frame[k] = res[k][index]
+            out["pointwise"] = frame
         return out
 
     # ------------------------------------------------------------------ LHS survey

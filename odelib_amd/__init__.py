@@ -5,7 +5,7 @@
 Compute runs only in libodelib_amd.so (HIP, gfx950); see DESIGN.md.
 """
 from . import Statistics  # noqa: F401
-from .Framework import ModelFramework, parameter, rawstats  # noqa: F401
+from .Framework import ModelFramework, compare, parameter, rawstats  # noqa: F401
 from .engine import Engine, FitProblem  # noqa: F401
 
 __version__ = "0.1.0"

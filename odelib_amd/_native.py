@@ -63,6 +63,9 @@ EXPORTED = (
     "oe_band_hist",
     "oe_band_quantiles",
     "oe_diag_run",
+    "oe_waic_begin",
+    "oe_waic_accum",
+    "oe_waic_finish",
 )
 
 
@@ -142,6 +145,12 @@ class OEDiagArgs(C.Structure):
 
 # the fields of a row of oe_diag_run's summary, in order
 DIAG_FIELDS = ("n_chains", "n", "mean", "W", "B", "var_plus", "rhat", "tau", "ess", "mcse", "stop_lag", "truncated")
+
+
+# the cells, pointwise columns and summary fields of the oe_waic_* calls, in order
+WAIC_ACC = 5
+WAIC_POINT_FIELDS = ("n", "lppd", "p_waic", "elpd", "mean_ll", "max_ll")
+WAIC_SUMMARY_FIELDS = ("n_obs_used", "lppd", "p_waic", "elpd_waic", "waic", "se_elpd", "n_high_var", "n_rows_min")
 
 
 _lib = None
@@ -227,6 +236,12 @@ def load_library(path: str | None = None):
         lib.oe_band_quantiles.argtypes = [vp, vp, vp, i32, vp, vp, u32]
         lib.oe_diag_run.restype = C.c_int
         lib.oe_diag_run.argtypes = [vp, C.POINTER(OEDiagArgs), u32]
+        lib.oe_waic_begin.restype = C.c_int
+        lib.oe_waic_begin.argtypes = [vp, vp]
+        lib.oe_waic_accum.restype = C.c_int
+        lib.oe_waic_accum.argtypes = [vp, i64, vp, vp, vp, i64, i64, u32]
+        lib.oe_waic_finish.restype = C.c_int
+        lib.oe_waic_finish.argtypes = [vp, vp, vp, vp, u32]
         if lib.oe_abi_version() != OE_ABI_VERSION:
             raise NativeUnavailable("libodelib_amd.so ABI version mismatch; rebuild it")
         if path is None:
@@ -332,6 +347,19 @@ class Context:
                        rows=r.ctypes.data, log_rows=lg.ctypes.data, max_lag=int(max_lag), summary=summary, rho=rho,
                        chain_stats=chain_stats)
         self._check(self.lib.oe_diag_run(self._h, C.byref(a), int(flags)), "oe_diag_run")
+
+    def waic_begin(self, acc):
+        """``oe_waic_begin``: ``acc`` a device pointer to [n_obs][5] doubles."""
+        self._check(self.lib.oe_waic_begin(self._h, acc), "oe_waic_begin")
+
+    def waic_accum(self, n_walkers, traj, acc, terms=None, terms_ld=0, w_offset=0, flags=0):
+        """``oe_waic_accum``: device pointers; ``terms`` [n_obs][terms_ld] or None."""
+        self._check(self.lib.oe_waic_accum(self._h, int(n_walkers), traj, acc, terms, int(terms_ld), int(w_offset),
+                                           int(flags)), "oe_waic_accum")
+
+    def waic_finish(self, acc, pointwise, summary, flags=0):
+        """``oe_waic_finish``: device pointers; ``pointwise`` [n_obs][6], ``summary`` [8]."""
+        self._check(self.lib.oe_waic_finish(self._h, acc, pointwise, summary, int(flags)), "oe_waic_finish")
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)

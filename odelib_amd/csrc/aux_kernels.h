@@ -6,6 +6,7 @@
 #include "diag.cuh"
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
+#include "waic.cuh"
 
 // deepest tree k_mh_resolve_wave holds in LDS (4 095 nodes)
 constexpr int kResolveLdsDepth = 12;
@@ -28,3 +29,8 @@ __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_moments(const oe::DiagA
 __global__ void __launch_bounds__(64) k_diag_merge(const oe::DiagArgs a);
 __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_acov(const oe::DiagArgs a);
 __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_eval(const oe::DiagArgs a);
+// posterior-wide model comparison (waic.cuh): pointwise log-likelihoods reduced across walkers
+__global__ void __launch_bounds__(256) k_waic_init(double* __restrict__ acc, int64_t n_cells);
+__global__ void __launch_bounds__(oe::kBandBlock) k_waic_accum(const oe::WaicArgs a);
+__global__ void __launch_bounds__(256) k_waic_merge(const oe::WaicArgs a);
+__global__ void __launch_bounds__(256) k_waic_finish(const oe::WaicArgs a);

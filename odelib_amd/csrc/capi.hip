@@ -60,7 +60,7 @@ static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRe
                   plan::kHandBdfWaves == kHandBdfWaves && plan::kResolveLdsDepth == kResolveLdsDepth &&
                   plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile &&
                   plan::kDiagBlock == kDiagBlock && plan::kDiagLB == kDiagLB && plan::kDiagPart == kDiagPart &&
-                  plan::kDiagState == kDiagState,
+                  plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc,
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -121,9 +121,18 @@ struct oe_ctx {
   DevBuf band_part;  // k_band_moments' partials, one cell per workgroup and column
   DevBuf band_tab;   // the band's column masks [64] uint64, then its quantiles [64] doubles
   DevBuf diag;       // oe_diag_run's scratch (launch_plan.h DiagPlan)
-  std::array<DevBuf*, 10> bufs() {
-    return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag};
+  DevBuf waic_part;  // k_waic_accum's partials, one cell per workgroup
+  DevBuf waic_tab;   // the comparison's tables: c_o [n_obs] doubles (record order), then perm [n_obs] int32
+  std::array<DevBuf*, 12> bufs() {
+    return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag, &waic_part,
+            &waic_tab};
   }
+  // model comparison (oe_waic_begin .. oe_waic_finish): per observation record (sorted by grid
+  // index, as d_obs) the Gaussian normaliser c_o = -(log s_o + log(2 pi)/2) and the caller's
+  // index of the record, kept by oe_problem_set
+  std::vector<double> waic_c;
+  std::vector<int32_t> waic_perm;
+  bool waic_on = false;  // a pass begun for the current problem
   // posterior bands (oe_band_begin .. oe_band_quantiles); the tables' host copies live here so
   // an asynchronous upload never reads the caller's arrays after the call
   int32_t band_cols = 0, band_bins = 0;  // 0: no band begun for the current problem
@@ -563,14 +572,14 @@ int oe_problem_set(oe_ctx* c, const oe_problem* p) {
   if (p->n_obs > 0 && (!p->obs_tidx || !p->obs_mask || !p->obs_log || !p->obs_logsigma || !p->obs_lin))
     return fail(c, OE_ERR_ARG, "oe_problem_set: observation arrays missing");
 
-  std::vector<Obs> obs(p->n_obs);
+  std::vector<Obs> obs_in(p->n_obs);
   const uint64_t valid_mask = (e->S >= 64) ? ~0ull : ((1ull << e->S) - 1ull);
   for (int k = 0; k < p->n_obs; ++k) {
     if (p->obs_tidx[k] < 0 || p->obs_tidx[k] >= p->n_times)
       return fail(c, OE_ERR_ARG, "oe_problem_set: obs_tidx out of range");
     if (p->obs_mask[k] == 0 || (p->obs_mask[k] & ~valid_mask))
       return fail(c, OE_ERR_ARG, "oe_problem_set: obs_mask selects no / unknown states");
-    Obs& o = obs[k];
+    Obs& o = obs_in[k];
     o.tidx = p->obs_tidx[k];
     o.pad = 0;
     o.mask = p->obs_mask[k];
@@ -579,7 +588,16 @@ int oe_problem_set(oe_ctx* c, const oe_problem* p) {
     o.two_s2 = 2.0 * (s * s);
     o.O_lin = p->obs_lin[k];
   }
-  std::stable_sort(obs.begin(), obs.end(), [](const Obs& a, const Obs& b) { return a.tidx < b.tidx; });
+  // the records sorted by grid index (stable), and which observation of the caller's each is
+  std::vector<int32_t> perm(p->n_obs);
+  for (int k = 0; k < p->n_obs; ++k) perm[k] = k;
+  std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return obs_in[a].tidx < obs_in[b].tidx; });
+  std::vector<Obs> obs(p->n_obs);
+  std::vector<double> c_rec(p->n_obs);
+  for (int k = 0; k < p->n_obs; ++k) {
+    obs[k] = obs_in[perm[k]];
+    c_rec[k] = -(std::log(p->obs_logsigma[perm[k]]) + 0.5 * std::log(2.0 * 3.14159265358979323846));
+  }
 
   // RK4 per-interval constants: h = (t_i - t_{i-1}) / n, h/2, h/6, t_{i-1}
   // (IEEE-correctly-rounded on host and device alike, so the table is exact)
@@ -631,6 +649,9 @@ int oe_problem_set(oe_ctx* c, const oe_problem* p) {
   c->entry = e;
   c->has_problem = true;
   c->band_cols = c->band_bins = 0;  // a band belongs to the problem it was begun for
+  c->waic_on = false;               // and so does a comparison pass
+  c->waic_c = std::move(c_rec);
+  c->waic_perm = std::move(perm);
   c->err.clear();
   return OE_OK;
 }
@@ -1212,6 +1233,98 @@ int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
     OE_HIP(c, launch(kernel_of(k_diag_acov), dim3(pl.grid), dim3(pl.block), c->stream, a));
     OE_HIP(c, launch(kernel_of(k_diag_eval), dim3(pl.row_grid), dim3(kDiagBlock), c->stream, a));
   }
+  return band_finish(c, flags);
+}
+
+// ---- posterior-wide model comparison (waic.cuh) -----------------------
+namespace {
+
+int waic_state(oe_ctx* c, const char* who) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!c->has_problem) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_problem_set first");
+  if (!c->waic_on) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_waic_begin first");
+  return OE_OK;
+}
+
+WaicArgs waic_args(oe_ctx* c) {
+  WaicArgs a{};
+  a.obs = c->d_obs;
+  a.c_rec = static_cast<const double*>(c->waic_tab.p);
+  a.perm = reinterpret_cast<const int32_t*>(a.c_rec + c->dp.n_obs);
+  a.S = c->entry->S;
+  a.n_obs = c->dp.n_obs;
+  return a;
+}
+
+}  // namespace
+
+int oe_waic_begin(oe_ctx* c, double* acc) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!c->has_problem) return fail(c, OE_ERR_STATE, "oe_waic_begin: call oe_problem_set first");
+  const int n_obs = c->dp.n_obs;
+  if (n_obs < 1) return fail(c, OE_ERR_ARG, "oe_waic_begin: the problem has no observations");
+  if (!acc) return fail(c, OE_ERR_ARG, "oe_waic_begin: acc is required");
+  OE_DEVICE_GUARD(c);
+  c->waic_on = false;
+  const size_t c_bytes = sizeof(double) * (size_t)n_obs;
+  const int rc = c->waic_tab.reserve(c, c_bytes + sizeof(int32_t) * (size_t)n_obs);
+  if (rc) return rc;
+  // (the host vectors live in the context until the next oe_problem_set, which synchronizes)
+  char* tab = static_cast<char*>(c->waic_tab.p);
+  OE_HIP(c, hipMemcpyAsync(tab, c->waic_c.data(), c_bytes, hipMemcpyHostToDevice, c->stream));
+  OE_HIP(c, hipMemcpyAsync(tab + c_bytes, c->waic_perm.data(), sizeof(int32_t) * (size_t)n_obs, hipMemcpyHostToDevice,
+                           c->stream));
+  const plan::WaicPlan pl = plan::plan_waic(n_obs, 1, c->n_cu);
+  OE_HIP(c, launch(kernel_of(k_waic_init), dim3(pl.cell_grid), dim3(kBlock), c->stream, acc, (int64_t)n_obs));
+  OE_HIP(c, hipGetLastError());
+  OE_HIP(c, hipStreamSynchronize(c->stream));
+  c->waic_on = true;
+  return OE_OK;
+}
+
+int oe_waic_accum(oe_ctx* c, int64_t W, const double* traj, double* acc, double* terms, int64_t terms_ld,
+                  int64_t w_offset, uint32_t flags) {
+  int rc = waic_state(c, "oe_waic_accum");
+  if (rc) return rc;
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_waic_accum: device pointers only");
+  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_waic_accum: n_walkers must be in [1, 2^29]");
+  if (!traj || !acc) return fail(c, OE_ERR_ARG, "oe_waic_accum: traj and acc are required");
+  if (terms && (w_offset < 0 || terms_ld < 1 || w_offset > terms_ld - W))
+    return fail(c, OE_ERR_ARG, "oe_waic_accum: w_offset + n_walkers must be within terms_ld");
+  OE_DEVICE_GUARD(c);
+  const plan::WaicPlan pl = plan::plan_waic(c->dp.n_obs, W, band_cus(c));
+  rc = c->waic_part.reserve(c, pl.partial_bytes);
+  if (rc) return rc;
+  WaicArgs a = waic_args(c);
+  a.traj = traj;
+  a.acc = acc;
+  a.part = static_cast<double*>(c->waic_part.p);
+  a.terms = terms;
+  a.terms_ld = terms ? terms_ld : 0;
+  a.w_offset = terms ? w_offset : 0;
+  a.W = W;
+  a.per_block = pl.per_block;
+  a.bpo = pl.blocks_per_obs;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_waic_accum), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_waic_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
+  return band_finish(c, flags);
+}
+
+int oe_waic_finish(oe_ctx* c, const double* acc, double* pointwise, double* summary, uint32_t flags) {
+  const int rc = waic_state(c, "oe_waic_finish");
+  if (rc) return rc;
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_waic_finish: device pointers only");
+  if (!acc || !pointwise || !summary)
+    return fail(c, OE_ERR_ARG, "oe_waic_finish: acc, pointwise and summary are required");
+  OE_DEVICE_GUARD(c);
+  const plan::WaicPlan pl = plan::plan_waic(c->dp.n_obs, 1, c->n_cu);
+  WaicArgs a = waic_args(c);
+  a.acc = const_cast<double*>(acc);
+  a.pointwise = pointwise;
+  a.summary = summary;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_waic_finish), dim3(pl.finish_grid), dim3(pl.finish_block), c->stream, a));
   return band_finish(c, flags);
 }
 

@@ -1,6 +1,6 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
 // (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
-// posterior band reductions, the convergence diagnostics.
+// posterior band reductions, the convergence diagnostics, the model-comparison reductions.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -225,3 +225,11 @@ __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_moments(const oe::DiagA
 __global__ void __launch_bounds__(64) k_diag_merge(const oe::DiagArgs a) { oe::diag_merge(a); }
 __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_acov(const oe::DiagArgs a) { oe::diag_acov(a); }
 __global__ void __launch_bounds__(oe::kDiagBlock) k_diag_eval(const oe::DiagArgs a) { oe::diag_eval(a); }
+
+// posterior-wide model comparison: WAIC's pointwise reductions across walkers (waic.cuh)
+__global__ void __launch_bounds__(256) k_waic_init(double* __restrict__ acc, int64_t n_cells) {
+  oe::waic_init(acc, n_cells);
+}
+__global__ void __launch_bounds__(oe::kBandBlock) k_waic_accum(const oe::WaicArgs a) { oe::waic_accum(a); }
+__global__ void __launch_bounds__(256) k_waic_merge(const oe::WaicArgs a) { oe::waic_merge(a); }
+__global__ void __launch_bounds__(256) k_waic_finish(const oe::WaicArgs a) { oe::waic_finish(a); }

@@ -1,8 +1,8 @@
-// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes and oe_diag_run launch,
-// decided by pure functions: numbers in, a plan out (kernel, grids, half waves, XCD runs, the
-// hand-over queue's placement, speculation depth, chunk, lag blocks, buffer sizes).  No HIP here,
-// so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp and diag_plan_driver.cpp check the
-// arithmetic on the CPU;
+// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run and the
+// oe_waic_* passes launch, decided by pure functions: numbers in, a plan out (kernel, grids, half
+// waves, XCD runs, the hand-over queue's placement, speculation depth, chunk, lag blocks, walker
+// runs, buffer sizes).  No HIP here, so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp,
+// diag_plan_driver.cpp and waic_plan_driver.cpp check the arithmetic on the CPU;
 // capi.hip reserves, fills the arguments and launches.
 #pragma once
 #include <algorithm>
@@ -340,6 +340,33 @@ inline int64_t plan_band_chunk(int T, int S, int64_t W_total, int64_t budget_byt
   const int64_t fit = budget_bytes / per_walker / 256 * 256;
   const int64_t all = (W_total + 255) / 256 * 256;
   return std::max<int64_t>(256, std::min(fit, all));
+}
+
+// ---- oe_waic_* ----------------------------------------------------------------------
+constexpr int kWaicAcc = 5;  // doubles per accumulator cell and per partial
+
+struct WaicPlan {
+  unsigned grid = 0, block = kBandBlock;  // k_waic_accum: grid = n_obs * blocks_per_obs
+  int64_t per_block = 0;                  // consecutive walkers of one observation per workgroup
+  int32_t blocks_per_obs = 0;
+  size_t partial_bytes = 0;               // k_waic_accum's [n_obs][blocks_per_obs][5] doubles
+  unsigned cell_grid = 0;                 // k_waic_init / k_waic_merge: one lane per observation
+  unsigned finish_grid = 1, finish_block = kBlock;  // k_waic_finish: one workgroup, lanes strided
+};
+
+// k_waic_accum over a chunk traj [T][S][W]: workgroup (o, j) folds walkers
+// [j * per_block, min(W, (j + 1) * per_block)) of observation record o.  The observations are
+// the rows of this reduction: the run is plan_band_reduce's for n_obs rows, so one chunk size
+// serves the band and the comparison.
+inline WaicPlan plan_waic(int n_obs, int64_t W, int n_cu) {
+  WaicPlan p;
+  const BandPlan b = plan_band_reduce(n_obs, W, 1, n_cu);
+  p.per_block = b.per_block;
+  p.blocks_per_obs = b.blocks_per_row;
+  p.grid = b.grid;
+  p.partial_bytes = sizeof(double) * kWaicAcc * (size_t)n_obs * (size_t)p.blocks_per_obs;
+  p.cell_grid = (unsigned)(((int64_t)n_obs + kBlock - 1) / kBlock);
+  return p;
 }
 
 // ---- oe_diag_run --------------------------------------------------------------------

@@ -321,6 +321,37 @@ class Engine:
             torch.cuda.synchronize(self.dev)
         return {"traj": traj, "chi": chi, "ssres": ssres, "status": status}
 
+    # -- posterior rows streamed in chunks (band, waic) -----------------------------------------
+    def _chunk_spans(self, W: int, chunk=None):
+        """The walker spans [a, b) a posterior of W rows is streamed in (``chunk`` walkers each,
+        rounded up to a multiple of 256; default ``band_chunk``), and the one trajectory buffer
+        they reuse."""
+        pb = self.problem
+        T, S = pb.n_times, pb.n_states
+        Wc = band_chunk(T, S, W) if chunk is None else -(-int(chunk) // 256) * 256
+        Wc = min(max(Wc, 256), -(-W // 256) * 256)
+        spans = [(a, min(W, a + Wc)) for a in range(0, W, Wc)]
+        buf = self.torch.empty(T * S * min(W, Wc), dtype=self.torch.float64, device=self.dev)
+        return spans, buf
+
+    def _run_span(self, y0, theta, spans, buf, a, b, nt_stores, status=None):
+        """Integrate walkers [a, b) into the shared buffer; ``status``: the (OR, count) tensors
+        their status words are folded into.  Returns (walkers, traj [T][S][walkers])."""
+        torch = self.torch
+        T, S = self.problem.n_times, self.problem.n_states
+        w = b - a
+        traj = buf[:T * S * w].view(T, S, w)
+        whole = len(spans) == 1
+        res = self.integrate(y0 if whole else y0[:, a:b], theta if whole else theta[:, a:b], traj_out=traj,
+                             nt_stores=nt_stores, sync=False, timing=False)
+        if status is not None:
+            st_or, st_n = status
+            st = res["status"]
+            for bit in (1, 2, 4, 8, 16):
+                st_or.bitwise_or_(((st & bit) != 0).any().to(torch.int32) * bit)
+            st_n.add_((st != 0).sum())
+        return w, traj
+
     # -- posterior predictive bands -------------------------------------------------------------
     def band(self, y0, theta, quantiles, n_bins: int = 1024, chunk=None, col_masks=None, nt_stores: bool = True):
         """Summarise the trajectories of every walker (posterior row) per grid time and output
@@ -348,10 +379,7 @@ class Engine:
         masks = np.asarray([1 << s for s in range(S)] if col_masks is None else col_masks, dtype=np.uint64)
         q = np.ascontiguousarray(np.asarray(quantiles, dtype=np.float64).reshape(-1))
         n_cols, n_q = len(masks), len(q)
-        Wc = band_chunk(T, S, W) if chunk is None else -(-int(chunk) // 256) * 256
-        Wc = min(max(Wc, 256), -(-W // 256) * 256)
-        spans = [(a, min(W, a + Wc)) for a in range(0, W, Wc)]
-        buf = torch.empty(T * S * min(W, Wc), dtype=torch.float64, device=self.dev)
+        spans, buf = self._chunk_spans(W, chunk)
         acc = torch.empty((T, n_cols, 5), dtype=torch.float64, device=self.dev)
         hist = torch.empty((T, n_cols, int(n_bins)), dtype=torch.int32, device=self.dev)
         out = torch.empty((n_q, T, n_cols), dtype=torch.float64, device=self.dev)
@@ -361,17 +389,7 @@ class Engine:
         self.ctx.band_begin(masks, n_bins, _ptr(acc), _ptr(hist))
 
         def run(a, b, first):
-            w = b - a
-            traj = buf[:T * S * w].view(T, S, w)
-            whole = len(spans) == 1
-            res = self.integrate(y0 if whole else y0[:, a:b], theta if whole else theta[:, a:b], traj_out=traj,
-                                 nt_stores=nt_stores, sync=False, timing=False)
-            if first:
-                st = res["status"]
-                for bit in (1, 2, 4, 8, 16):
-                    st_or.bitwise_or_(((st & bit) != 0).any().to(torch.int32) * bit)
-                st_n.add_((st != 0).sum())
-            return w, traj
+            return self._run_span(y0, theta, spans, buf, a, b, nt_stores, (st_or, st_n) if first else None)
 
         for a, b in spans:
             w, traj = run(a, b, True)
@@ -388,6 +406,55 @@ class Engine:
         res["q"] = out.cpu().numpy()
         res["status_or"] = int(st_or.item())
         res["n_status"] = int(st_n.item())
+        return res
+
+    # -- posterior-wide model comparison -----------------------------------------------------------
+    def waic(self, y0, theta, chunk=None, terms: bool = False, nt_stores: bool = True):
+        """WAIC of the problem's observations over every walker (posterior row), without keeping
+        the trajectories (the estimator is stated at ``oe_waic_begin`` in
+        include/odelib_amd.h): y0 [S][W], theta [P][W] → dict of host arrays.
+
+        Per observation, in the problem's order ([n_obs]): ``n`` (int64, rows with a finite
+        term), ``lppd``, ``p_waic``, ``elpd``, ``mean_ll``, ``max_ll``; the sums as scalars under
+        ``summary`` (``n_obs_used``, ``lppd``, ``p_waic``, ``elpd_waic``, ``waic``, ``se_elpd``,
+        ``n_high_var``, ``n_rows_min``); plus ``status_or`` and ``n_status`` as ``band``.  The
+        rows go through ``integrate`` in ``band``'s chunks into one reused buffer, each chunk
+        folded once: the log-sum-exp is online, so there is one pass whatever the chunk count.
+        ``terms=True`` also returns ``terms``, the [n_obs][W] device tensor of every row's chi
+        term (NaN where it is not finite)."""
+        torch = self.torch
+        pb = self.problem
+        theta_t = theta if isinstance(theta, torch.Tensor) else np.asarray(theta)
+        W = int(theta_t.shape[1])
+        if W < 1:
+            raise ValueError("waic needs at least one walker")
+        if pb.n_obs < 1:
+            raise ValueError("waic needs a problem with observations")
+        y0 = self._dev(y0, (pb.n_states, W))
+        theta = self._dev(theta, (pb.n_params, W))
+        spans, buf = self._chunk_spans(W, chunk)
+        acc = torch.empty((pb.n_obs, N.WAIC_ACC), dtype=torch.float64, device=self.dev)
+        point = torch.empty((pb.n_obs, len(N.WAIC_POINT_FIELDS)), dtype=torch.float64, device=self.dev)
+        summary = torch.empty(len(N.WAIC_SUMMARY_FIELDS), dtype=torch.float64, device=self.dev)
+        terms_t = torch.empty((pb.n_obs, W), dtype=torch.float64, device=self.dev) if terms else None
+        st_or = torch.zeros((), dtype=torch.int32, device=self.dev)
+        st_n = torch.zeros((), dtype=torch.int64, device=self.dev)
+        self._sync_stream()
+        self.ctx.waic_begin(_ptr(acc))
+        for a, b in spans:
+            w, traj = self._run_span(y0, theta, spans, buf, a, b, nt_stores, (st_or, st_n))
+            self.ctx.waic_accum(w, _ptr(traj), _ptr(acc), _ptr(terms_t), W if terms else 0, a, N.OE_ASYNC)
+        self.ctx.waic_finish(_ptr(acc), _ptr(point), _ptr(summary), N.OE_ASYNC)
+        torch.cuda.synchronize(self.dev)
+        pw = point.cpu().numpy()
+        res = {name: pw[:, k].copy() for k, name in enumerate(N.WAIC_POINT_FIELDS)}
+        res["n"] = res["n"].astype(np.int64)
+        sm = summary.cpu().numpy()
+        res["summary"] = {name: float(sm[k]) for k, name in enumerate(N.WAIC_SUMMARY_FIELDS)}
+        res["status_or"] = int(st_or.item())
+        res["n_status"] = int(st_n.item())
+        if terms:
+            res["terms"] = terms_t
         return res
 
     # -- MCMC convergence diagnostics -------------------------------------------------------------

@@ -1043,11 +1043,20 @@ int oe_numpy_streams(oe_ctx* c, int64_t W, const uint32_t* seeds, int32_t nits, 
 // ---- posterior predictive bands (band.cuh) ----------------------------
 namespace {
 
-// what the three calls after oe_band_begin share: a problem set and a band begun
-int band_state(oe_ctx* c, const char* who) {
+// what the calls after a feature's begin share: a problem set and the feature begun
+int begun(oe_ctx* c, const char* who, bool on, const char* begin) {
   if (!c || !c->own_stream) return OE_ERR_STATE;
   if (!c->has_problem) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_problem_set first");
-  if (!c->band_cols) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_band_begin first");
+  if (!on) return fail(c, OE_ERR_STATE, std::string(who) + ": call " + begin + " first");
+  return OE_OK;
+}
+int band_begun(oe_ctx* c, const char* who) { return begun(c, who, c && c->band_cols, "oe_band_begin"); }
+int waic_begun(oe_ctx* c, const char* who) { return begun(c, who, c && c->waic_on, "oe_waic_begin"); }
+
+// device pointers only, and the walker count (of a call that takes one) in range
+int device_args(oe_ctx* c, const char* who, uint32_t flags, int64_t W = 1) {
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, std::string(who) + ": device pointers only");
+  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, std::string(who) + ": n_walkers must be in [1, 2^29]");
   return OE_OK;
 }
 
@@ -1077,7 +1086,8 @@ BandArgs band_args(oe_ctx* c, const plan::BandPlan& pl, int64_t W, const double*
   return a;
 }
 
-int band_finish(oe_ctx* c, uint32_t flags) {
+// the common end of a timed, possibly asynchronous launch sequence (ev0 recorded before it)
+int end_timed(oe_ctx* c, uint32_t flags) {
   OE_HIP(c, hipGetLastError());
   OE_HIP(c, hipEventRecord(c->ev1, c->stream));
   c->timed = true;
@@ -1119,10 +1129,9 @@ int oe_band_begin(oe_ctx* c, int32_t n_cols, const uint64_t* col_mask, int32_t n
 }
 
 int oe_band_moments(oe_ctx* c, int64_t W, const double* traj, double* acc, uint32_t flags) {
-  int rc = band_state(c, "oe_band_moments");
+  int rc = band_begun(c, "oe_band_moments");
+  if (!rc) rc = device_args(c, "oe_band_moments", flags, W);
   if (rc) return rc;
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_moments: device pointers only");
-  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_band_moments: n_walkers must be in [1, 2^29]");
   if (!traj || !acc) return fail(c, OE_ERR_ARG, "oe_band_moments: traj and acc are required");
   OE_DEVICE_GUARD(c);
   const plan::BandPlan pl = plan::plan_band_reduce(c->dp.T, W, c->band_cols, band_cus(c));
@@ -1132,28 +1141,27 @@ int oe_band_moments(oe_ctx* c, int64_t W, const double* traj, double* acc, uint3
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_band_moments), dim3(pl.grid), dim3(pl.block), c->stream, a));
   OE_HIP(c, launch(kernel_of(k_band_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 int oe_band_hist(oe_ctx* c, int64_t W, const double* traj, const double* acc, uint32_t* hist, uint32_t flags) {
-  const int rc = band_state(c, "oe_band_hist");
+  int rc = band_begun(c, "oe_band_hist");
+  if (!rc) rc = device_args(c, "oe_band_hist", flags, W);
   if (rc) return rc;
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_hist: device pointers only");
-  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_band_hist: n_walkers must be in [1, 2^29]");
   if (!traj || !acc || !hist) return fail(c, OE_ERR_ARG, "oe_band_hist: traj, acc and hist are required");
   OE_DEVICE_GUARD(c);
   const plan::BandPlan pl = plan::plan_band_reduce(c->dp.T, W, c->band_cols, band_cus(c));
   const BandArgs a = band_args(c, pl, W, traj, const_cast<double*>(acc), hist);
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_band_hist), dim3(pl.grid), dim3(pl.block), c->stream, a));
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 int oe_band_quantiles(oe_ctx* c, const double* acc, const uint32_t* hist, int32_t n_q, const double* q, double* out,
                       uint32_t flags) {
-  const int rc = band_state(c, "oe_band_quantiles");
+  int rc = band_begun(c, "oe_band_quantiles");
+  if (!rc) rc = device_args(c, "oe_band_quantiles", flags);
   if (rc) return rc;
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_band_quantiles: device pointers only");
   if (!acc || !hist || !q || !out) return fail(c, OE_ERR_ARG, "oe_band_quantiles: acc, hist, q and out are required");
   if (n_q < 1 || n_q > kBandMaxQ) return fail(c, OE_ERR_ARG, "oe_band_quantiles: n_q must be in [1, 64]");
   for (int k = 0; k < n_q; ++k)
@@ -1176,19 +1184,21 @@ int oe_band_quantiles(oe_ctx* c, const double* acc, const uint32_t* hist, int32_
   const int64_t n = (int64_t)a.T * a.n_cols * n_q;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_band_quantiles), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), c->stream, a));
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 // ---- MCMC convergence diagnostics (diag.cuh) --------------------------
 int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
   if (!c || !c->own_stream) return OE_ERR_STATE;
   if (!g) return fail(c, OE_ERR_ARG, "oe_diag_run: args is null");
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_diag_run: device pointers only");
+  int rc = device_args(c, "oe_diag_run", flags);
+  if (rc) return rc;
   if (!g->samples || !g->summary || !g->rows)
     return fail(c, OE_ERR_ARG, "oe_diag_run: samples, summary and rows are required");
   if (g->K < 8) return fail(c, OE_ERR_ARG, "oe_diag_run: K must be at least 8 kept draws");
   const int64_t W = g->n_walkers;
-  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_diag_run: n_walkers must be in [1, 2^29]");
+  rc = device_args(c, "oe_diag_run", 0, W);
+  if (rc) return rc;
   if (g->n_sel < 1 || g->n_sel > kDiagMaxRows) return fail(c, OE_ERR_ARG, "oe_diag_run: n_sel must be in [1, 64]");
   if (g->R_tot < 1) return fail(c, OE_ERR_ARG, "oe_diag_run: R_tot must be positive");
   for (int r = 0; r < g->n_sel; ++r)
@@ -1198,7 +1208,7 @@ int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
     return fail(c, OE_ERR_ARG, "oe_diag_run: max_lag must be in [1, K/2 - 1], or 0 for K/2 - 1");
   OE_DEVICE_GUARD(c);
   const plan::DiagPlan pl = plan::plan_diag(g->K, W, g->n_sel, g->max_lag);
-  const int rc = c->diag.reserve(c, pl.bytes);
+  rc = c->diag.reserve(c, pl.bytes);
   if (rc) return rc;
   char* base = static_cast<char*>(c->diag.p);
   DiagArgs a{};
@@ -1233,18 +1243,11 @@ int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
     OE_HIP(c, launch(kernel_of(k_diag_acov), dim3(pl.grid), dim3(pl.block), c->stream, a));
     OE_HIP(c, launch(kernel_of(k_diag_eval), dim3(pl.row_grid), dim3(kDiagBlock), c->stream, a));
   }
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 // ---- posterior-wide model comparison (waic.cuh) -----------------------
 namespace {
-
-int waic_state(oe_ctx* c, const char* who) {
-  if (!c || !c->own_stream) return OE_ERR_STATE;
-  if (!c->has_problem) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_problem_set first");
-  if (!c->waic_on) return fail(c, OE_ERR_STATE, std::string(who) + ": call oe_waic_begin first");
-  return OE_OK;
-}
 
 WaicArgs waic_args(oe_ctx* c) {
   WaicArgs a{};
@@ -1284,10 +1287,9 @@ int oe_waic_begin(oe_ctx* c, double* acc) {
 
 int oe_waic_accum(oe_ctx* c, int64_t W, const double* traj, double* acc, double* terms, int64_t terms_ld,
                   int64_t w_offset, uint32_t flags) {
-  int rc = waic_state(c, "oe_waic_accum");
+  int rc = waic_begun(c, "oe_waic_accum");
+  if (!rc) rc = device_args(c, "oe_waic_accum", flags, W);
   if (rc) return rc;
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_waic_accum: device pointers only");
-  if (W < 1 || W > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_waic_accum: n_walkers must be in [1, 2^29]");
   if (!traj || !acc) return fail(c, OE_ERR_ARG, "oe_waic_accum: traj and acc are required");
   if (terms && (w_offset < 0 || terms_ld < 1 || w_offset > terms_ld - W))
     return fail(c, OE_ERR_ARG, "oe_waic_accum: w_offset + n_walkers must be within terms_ld");
@@ -1308,13 +1310,13 @@ int oe_waic_accum(oe_ctx* c, int64_t W, const double* traj, double* acc, double*
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_waic_accum), dim3(pl.grid), dim3(pl.block), c->stream, a));
   OE_HIP(c, launch(kernel_of(k_waic_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 int oe_waic_finish(oe_ctx* c, const double* acc, double* pointwise, double* summary, uint32_t flags) {
-  const int rc = waic_state(c, "oe_waic_finish");
+  int rc = waic_begun(c, "oe_waic_finish");
+  if (!rc) rc = device_args(c, "oe_waic_finish", flags);
   if (rc) return rc;
-  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, "oe_waic_finish: device pointers only");
   if (!acc || !pointwise || !summary)
     return fail(c, OE_ERR_ARG, "oe_waic_finish: acc, pointwise and summary are required");
   OE_DEVICE_GUARD(c);
@@ -1325,7 +1327,7 @@ int oe_waic_finish(oe_ctx* c, const double* acc, double* pointwise, double* summ
   a.summary = summary;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_waic_finish), dim3(pl.finish_grid), dim3(pl.finish_block), c->stream, a));
-  return band_finish(c, flags);
+  return end_timed(c, flags);
 }
 
 int oe_last_kernel_ms(oe_ctx* c, double* ms) {

@@ -9,7 +9,7 @@
 //   k_diag_moments  per (row, chain): validity, then per half the mean m_j (a shifted sum) and
 //                   M2 = Σ(x − m_j)² in a second, centred pass; s_j² = M2/(n−1).  Across chains:
 //                   the Chan merge of the m_j (count, grand mean, Σ(m_j − m̄)²: that is B) and of
-//                   the s_j² (their mean is W̄), band.cuh's Mom / mom_merge / mom_wave.
+//                   the s_j² (their mean is W̄), reduce.cuh's Welford.
 //   k_diag_merge    one workgroup per row: the workgroups' partials in block order, then the
 //                   summary's first seven fields; a degenerate row (M = 0, W̄ = 0 or not finite)
 //                   is finished here and marked done.
@@ -24,11 +24,10 @@
 //                   truncated and a plain store to its `done` word.
 // The host enqueues moments, merge and every (acov, eval) pair up front; the later launches
 // return at once for a row that is done.  One lane is one chain, so a wave's load of a draw is
-// 512 contiguous bytes.  Every floating-point sum across chains runs in a fixed order — lane,
-// wave (DPP), workgroup (LDS), workgroups in block order — without atomics: the same bits run
-// to run.
+// 512 contiguous bytes.  Every floating-point sum across chains runs in reduce.cuh's fixed order:
+// the same bits run to run.
 #pragma once
-#include "band.cuh"
+#include "reduce.cuh"
 
 namespace oe {
 
@@ -68,21 +67,6 @@ __device__ __forceinline__ double diag_g(double v) {
 
 __device__ __forceinline__ bool diag_finite(double v) { return fabs(v) < __builtin_inf(); }
 
-// lane 63 holds the sum of the wave's 64 values, added in mom_wave's order
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ double sum_hop(double a) {
-  return a + dpp_f64<CTRL, ROW_MASK>(a);
-}
-__device__ __forceinline__ double sum_wave(double a) {
-  a = sum_hop<0xB1>(a);
-  a = sum_hop<0x4E>(a);
-  a = sum_hop<0x141>(a);
-  a = sum_hop<0x140>(a);
-  a = sum_hop<0x142, 0xA>(a);
-  a = sum_hop<0x143, 0xC>(a);
-  return a;
-}
-
 // one chain's two halves: validity over all K draws, shifted means, centred M2
 template <bool LOG>
 __device__ __forceinline__ void diag_chain(const double* __restrict__ p, int64_t stride, int K, int n, bool& fin,
@@ -115,7 +99,7 @@ __device__ __forceinline__ void diag_chain(const double* __restrict__ p, int64_t
 }
 
 __device__ __forceinline__ void diag_moments(const DiagArgs& a) {
-  __shared__ Mom s_wave[2][kDiagBlock / 64];
+  __shared__ Welford s_wave[2][kDiagBlock / 64];
   const int r = (int)(blockIdx.x / (unsigned)a.bpr), j = (int)(blockIdx.x - (unsigned)r * (unsigned)a.bpr);
   const int t = threadIdx.x;
   const int64_t w = (int64_t)j * kDiagBlock + t;
@@ -144,32 +128,21 @@ __device__ __forceinline__ void diag_moments(const DiagArgs& a) {
     }
   }
   // across chains: (w, 0) then (w, 1) per lane, then wave, workgroup (all 64 lanes of every wave)
-  Mom mm = mom_empty(), ms = mom_empty();
+  Welford mm{0.0, 0.0, 0.0}, ms{0.0, 0.0, 0.0};
   if (valid) {
-    mom_push(mm, m[0], m[0]);
-    mom_push(mm, m[1], m[1]);
-    mom_push(ms, s0, s0);
-    mom_push(ms, s1, s1);
+    mm.push(m[0]);
+    mm.push(m[1]);
+    ms.push(s0);
+    ms.push(s1);
   }
-  mm = mom_wave(mm);
-  ms = mom_wave(ms);
-  if ((t & 63) == 63) {
-    s_wave[0][t >> 6] = mm;
-    s_wave[1][t >> 6] = ms;
-  }
-  __syncthreads();
+  mm = block_fold(s_wave[0], mm);
+  ms = block_fold(s_wave[1], ms);
   if (t == 0) {
-    Mom rm = s_wave[0][0], rs = s_wave[1][0];
-#pragma unroll
-    for (int k = 1; k < kDiagBlock / 64; ++k) {
-      rm = mom_merge(rm, s_wave[0][k]);
-      rs = mom_merge(rs, s_wave[1][k]);
-    }
     double* q = a.mpart + ((int64_t)r * a.bpr + j) * kDiagPart;
-    q[0] = rm.n;
-    q[1] = rm.mean;
-    q[2] = rm.m2;
-    q[3] = rs.mean;
+    q[0] = mm.n;
+    q[1] = mm.mean;
+    q[2] = mm.m2;
+    q[3] = ms.mean;
   }
 }
 
@@ -181,12 +154,13 @@ __device__ __forceinline__ void diag_merge(const DiagArgs& a) {
   if (a.rho)
     for (int l = 1 + t; l <= a.max_lag; l += 64) a.rho[(int64_t)r * (a.max_lag + 1) + l] = nan;
   if (t != 0) return;
-  Mom rm = mom_empty(), rs = mom_empty();
-  for (int j = 0; j < a.bpr; ++j) {
-    const double* q = a.mpart + ((int64_t)r * a.bpr + j) * kDiagPart;
-    rm = mom_merge(rm, Mom{q[0], q[1], q[2], q[1], q[1]});
-    rs = mom_merge(rs, Mom{q[0], q[3], 0.0, q[3], q[3]});
-  }
+  const double* q = a.mpart + (int64_t)r * a.bpr * kDiagPart;
+  const Welford rm = merge_partials(Welford{0.0, 0.0, 0.0}, a.bpr, [&](int j) {
+    return Welford{q[j * kDiagPart], q[j * kDiagPart + 1], q[j * kDiagPart + 2]};
+  });
+  const Welford rs = merge_partials(Welford{0.0, 0.0, 0.0}, a.bpr, [&](int j) {
+    return Welford{q[j * kDiagPart], q[j * kDiagPart + 3], 0.0};
+  });
   const double M = rm.n, n = (double)a.n;
   double* s = a.summary + (int64_t)r * kDiagSummary;
   double* st = a.state + (int64_t)r * kDiagState;
@@ -278,7 +252,7 @@ __device__ __forceinline__ void diag_acov(const DiagArgs& a) {
   const double inv_n = 1.0 / (double)a.n;
 #pragma unroll
   for (int l = 0; l < kDiagLB; ++l) {
-    const double v = sum_wave(valid ? acc[l] * inv_n : 0.0);  // an invalid chain's sums are dropped
+    const double v = wave_fold(Sum{valid ? acc[l] * inv_n : 0.0}).v;  // an invalid chain's sums are dropped
     if ((t & 63) == 63) s_part[t >> 6][l] = v;
   }
   __syncthreads();

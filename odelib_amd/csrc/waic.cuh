@@ -6,18 +6,16 @@
 //   C = Σ_{s∈mask} y_s (band_columns: from 0.0, increasing state order), d = O − log C,
 //   term = (d·d)/two_s2 (observe()'s operations), valid iff term is finite, e = −term.
 // Per record one cell of five doubles over the valid elements of every chunk folded so far:
-//   n, mean e, M2 e (Welford / Chan, as band.cuh's moments), a = max e, s = Σ exp(e − a):
+//   n, mean e, M2 e (reduce.cuh's Welford), a = max e, s = Σ exp(e − a):
 //   the online log-sum-exp, so one pass serves any number of chunks.
 //   k_waic_init                     the empty cells (0, 0, 0, −inf, 0)
 //   k_waic_accum + k_waic_merge     a chunk folded into the cells; optionally term stored
 //   k_waic_finish                   the pointwise outputs and their sums, in the caller's order
-// Tiling as band.cuh's passes: a workgroup takes one record and a run of consecutive walkers
-// (launch_plan.h plan_waic: plan_band_reduce's run), 512 contiguous bytes per wave-instruction,
-// four loads in flight per state and lane.  Merges run in a fixed order — lane, wave (DPP),
-// workgroup (LDS, wave order), the workgroups' partials in block order — without
-// floating-point atomics: every output is the same bits run to run for one chunking.
+// Tiled by reduce.cuh's walker runs, one record and run per workgroup (launch_plan.h plan_waic:
+// plan_band_reduce's run).  Merges run in reduce.cuh's fixed order: every output is the same bits
+// run to run for one chunking.
 #pragma once
-#include "band.cuh"
+#include "reduce.cuh"
 
 namespace oe {
 
@@ -43,121 +41,78 @@ struct WaicArgs {
   int32_t bpo;          // workgroups per record
 };
 
-struct Lse {
-  double n, mean, m2, a, s;
-};
-
 // exp out of line: inlined into k_waic_accum's loop and wave merge its constants stay resident
 // in VGPRs beside log's (78 VGPRs, 6 waves per SIMD); called, the kernel needs 60 and keeps 8
 __device__ __attribute__((noinline)) inline double lse_exp(double x) { return exp(x); }
 
-__device__ __forceinline__ Lse lse_empty() { return Lse{0.0, 0.0, 0.0, -__builtin_inf(), 0.0}; }
+// Welford of e with the online log-sum-exp (a = max e, s = Σ exp(e − a)): five doubles, the
+// accumulator cell's layout
+struct Lse : Welford {
+  double a, s;
+  // one more element; the shifted sum of exponentials is s·exp(a − e) + 1 with a = e if e > a,
+  // else s + exp(e − a): one exponential either way (a = −inf, s = 0 takes the first branch)
+  __device__ __forceinline__ void push(double e) {
+    Welford::push(e);
+    const bool up = e > a;
+    const double x = lse_exp(up ? a - e : e - a);
+    s = up ? s * x + 1.0 : s + x;
+    a = up ? e : a;
+  }
+  static __device__ __forceinline__ Lse load(const double* p) { return Lse{{p[0], p[1], p[2]}, p[3], p[4]}; }
+  __device__ __forceinline__ void store(double* p) const {
+    p[0] = n;
+    p[1] = mean;
+    p[2] = m2;
+    p[3] = a;
+    p[4] = s;
+  }
+};
 
-// one more element: Welford as mom_push, then the shifted sum of exponentials (a = −inf, s = 0
-// takes the first branch: s = 0·exp(−inf) + 1)
-__device__ __forceinline__ void lse_push(Lse& c, double e) {
-  c.n += 1.0;
-  const double d = e - c.mean;
-  c.mean += d / c.n;
-  c.m2 += d * (e - c.mean);
-  // s·exp(a − e) + 1 with a = e if e > a, else s + exp(e − a): one exponential either way
-  const bool up = e > c.a;
-  const double x = lse_exp(up ? c.a - e : e - c.a);
-  c.s = up ? c.s * x + 1.0 : c.s + x;
-  c.a = up ? e : c.a;
-}
+__device__ __forceinline__ Lse lse_empty() { return Lse{{0.0, 0.0, 0.0}, -__builtin_inf(), 0.0}; }
 
-// a then b: Chan as mom_merge; m = max(a_A, a_B), s = s_A·exp(a_A − m) + s_B·exp(a_B − m).  An
-// empty side leaves the other's bits as they are, and −inf − (−inf) is never formed.
-__device__ __forceinline__ Lse lse_merge(const Lse& a, const Lse& b) {
-  Lse r;
-  r.n = a.n + b.n;
-  const double d = b.mean - a.mean;
-  const double rb = b.n / r.n;
-  const double mean = a.mean + d * rb;
-  const double m2 = (a.m2 + b.m2) + (d * d) * (a.n * rb);
+// a then b: m = max(a_A, a_B), s = s_A·exp(a_A − m) + s_B·exp(a_B − m).  An empty side leaves
+// the other's bits as they are, and −inf − (−inf) is never formed.
+__device__ __forceinline__ Lse merge(const Lse& a, const Lse& b) {
   const bool ae = a.n == 0.0, be = b.n == 0.0;
-  r.mean = be ? a.mean : ae ? b.mean : mean;
-  r.m2 = be ? a.m2 : ae ? b.m2 : m2;
   // (the side holding the maximum is scaled by exp(0) = 1 exactly: one exponential serves)
   const double m = fmax(a.a, b.a);
   const bool a_top = a.a >= b.a;
   const double x = lse_exp((ae || be) ? 0.0 : a_top ? b.a - a.a : a.a - b.a);
   const double s = a_top ? a.s + b.s * x : a.s * x + b.s;
-  r.a = m;
-  r.s = be ? a.s : ae ? b.s : s;
-  return r;
+  return Lse{merge(static_cast<const Welford&>(a), static_cast<const Welford&>(b)), m, be ? a.s : ae ? b.s : s};
 }
 
-template <int CTRL, int ROW_MASK = 0xF>
-__device__ __forceinline__ Lse lse_hop(const Lse& a) {
-  const Lse b{dpp_f64<CTRL, ROW_MASK>(a.n), dpp_f64<CTRL, ROW_MASK>(a.mean), dpp_f64<CTRL, ROW_MASK>(a.m2),
-              dpp_f64<CTRL, ROW_MASK>(a.a), dpp_f64<CTRL, ROW_MASK>(a.s)};
-  return lse_merge(a, b);
-}
-
-// mom_wave's hops: lane 63 holds the wave's cell, all 64 lanes must be active
-__device__ __forceinline__ Lse lse_wave(Lse a) {
-  a = lse_hop<0xB1>(a);
-  a = lse_hop<0x4E>(a);
-  a = lse_hop<0x141>(a);
-  a = lse_hop<0x140>(a);
-  a = lse_hop<0x142, 0xA>(a);
-  a = lse_hop<0x143, 0xC>(a);
-  return a;
-}
-
-__device__ __forceinline__ Lse lse_load(const double* p) { return Lse{p[0], p[1], p[2], p[3], p[4]}; }
-__device__ __forceinline__ void lse_store(double* p, const Lse& c) {
-  p[0] = c.n;
-  p[1] = c.mean;
-  p[2] = c.m2;
-  p[3] = c.a;
-  p[4] = c.s;
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ Lse shifted(const Lse& a) {
+  return Lse{shifted<CTRL, ROW_MASK>(static_cast<const Welford&>(a)), dpp_f64<CTRL, ROW_MASK>(a.a),
+             dpp_f64<CTRL, ROW_MASK>(a.s)};
 }
 
 __device__ __forceinline__ void waic_init(double* __restrict__ acc, int64_t n_cells) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_cells) return;
-  lse_store(acc + g * kWaicAcc, lse_empty());
+  if (g < n_cells) lse_empty().store(acc + g * kWaicAcc);
 }
 
 __device__ __forceinline__ void waic_accum(const WaicArgs& a) {
   __shared__ Lse s_wave[kBandBlock / 64];
-  const int o = (int)(blockIdx.x / (unsigned)a.bpo), j = (int)(blockIdx.x - (unsigned)o * (unsigned)a.bpo);
-  const int64_t w0 = (int64_t)j * a.per_block;
-  const int64_t w1 = w0 + a.per_block < a.W ? w0 + a.per_block : a.W;
+  const WalkerRun run = walker_run(a.bpo, a.per_block, a.W);
+  const int o = run.row;
   const cptr<Obs> obs = kconst(a.obs);
-  const uint64_t mask = obs[o].mask;
   const double O = obs[o].O, two_s2 = obs[o].two_s2;
   const double* row = a.traj + (int64_t)obs[o].tidx * a.S * a.W;
   double* trow = a.terms ? a.terms + (int64_t)kconst(a.perm)[o] * a.terms_ld + a.w_offset : nullptr;
-  const int t = threadIdx.x;
   Lse c = lse_empty();
-  for (int64_t w = w0 + t; w < w1; w += kBandTile) {
-    double v[kBandUnroll];
-    band_columns(row, a.W, mask, w, w1, v);
-#pragma unroll
-    for (int u = 0; u < kBandUnroll; ++u) {
-      const int64_t wu = w + (int64_t)u * kBandBlock;
-      if (wu < w1) {
-        const double d = O - log(v[u]);
-        const double term = (d * d) / two_s2;
-        const bool valid = __builtin_isfinite(term);
-        if (valid) lse_push(c, -term);
-        if (trow) trow[wu] = valid ? term : __builtin_nan("");
-      }
+  for_each_walker(row, a.W, obs[o].mask, run, [&](double v, int64_t w) {
+    if (w < run.w1) {
+      const double d = O - log(v);
+      const double term = (d * d) / two_s2;
+      const bool valid = __builtin_isfinite(term);
+      if (valid) c.push(-term);
+      if (trow) trow[w] = valid ? term : __builtin_nan("");
     }
-  }
-  c = lse_wave(c);
-  if ((t & 63) == 63) s_wave[t >> 6] = c;
-  __syncthreads();
-  if (t == 0) {
-    Lse r = s_wave[0];
-#pragma unroll
-    for (int k = 1; k < kBandBlock / 64; ++k) r = lse_merge(r, s_wave[k]);
-    lse_store(a.part + ((int64_t)o * a.bpo + j) * kWaicAcc, r);
-  }
+  });
+  c = block_fold(s_wave, c);
+  if (threadIdx.x == 0) c.store(a.part + ((int64_t)o * a.bpo + run.j) * kWaicAcc);
 }
 
 // the workgroups' partials of one record, in block order, into the accumulator
@@ -165,9 +120,8 @@ __device__ __forceinline__ void waic_merge(const WaicArgs& a) {
   const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= a.n_obs) return;
   double* cell = a.acc + o * kWaicAcc;
-  Lse r = lse_load(cell);
-  for (int j = 0; j < a.bpo; ++j) r = lse_merge(r, lse_load(a.part + (o * a.bpo + j) * kWaicAcc));
-  lse_store(cell, r);
+  merge_partials(Lse::load(cell), a.bpo, [&](int j) { return Lse::load(a.part + (o * a.bpo + j) * kWaicAcc); })
+      .store(cell);
 }
 
 // One workgroup.  Lane o (strided over the records) writes the pointwise outputs of its record
@@ -175,7 +129,7 @@ __device__ __forceinline__ void waic_merge(const WaicArgs& a) {
 __device__ __forceinline__ void waic_finish(const WaicArgs& a) {
   const double nan = __builtin_nan("");
   for (int o = threadIdx.x; o < a.n_obs; o += blockDim.x) {
-    const Lse c = lse_load(a.acc + (int64_t)o * kWaicAcc);
+    const Lse c = Lse::load(a.acc + (int64_t)o * kWaicAcc);
     const double co = a.c_rec[o];
     const bool some = c.n > 0.0, two = c.n > 1.0;
     const double lppd = some ? (c.a + log(c.s / c.n)) + co : nan;

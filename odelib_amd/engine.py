@@ -352,6 +352,32 @@ class Engine:
             st_n.add_((st != 0).sum())
         return w, traj
 
+    def _posterior_begin(self, what, y0, theta, chunk):
+        """The opening ``band`` and ``waic`` share: W from theta [P][W], y0 and theta on the
+        device, the chunk spans with their trajectory buffer, the zeroed (OR, count) status
+        tensors, and the library on the current stream.
+        Returns (W, y0, theta, spans, buf, status)."""
+        torch = self.torch
+        pb = self.problem
+        theta_t = theta if isinstance(theta, torch.Tensor) else np.asarray(theta)
+        W = int(theta_t.shape[1])
+        if W < 1:
+            raise ValueError(f"{what} needs at least one walker")
+        y0 = self._dev(y0, (pb.n_states, W))
+        theta = self._dev(theta, (pb.n_params, W))
+        spans, buf = self._chunk_spans(W, chunk)
+        status = (torch.zeros((), dtype=torch.int32, device=self.dev),
+                  torch.zeros((), dtype=torch.int64, device=self.dev))
+        self._sync_stream()
+        return W, y0, theta, spans, buf, status
+
+    @staticmethod
+    def _status_result(res, status):
+        """``status_or`` and ``n_status`` of the walkers folded into ``status``, read back."""
+        res["status_or"] = int(status[0].item())
+        res["n_status"] = int(status[1].item())
+        return res
+
     # -- posterior predictive bands -------------------------------------------------------------
     def band(self, y0, theta, quantiles, n_bins: int = 1024, chunk=None, col_masks=None, nt_stores: bool = True):
         """Summarise the trajectories of every walker (posterior row) per grid time and output
@@ -368,28 +394,18 @@ class Engine:
         bins), a second that integrates them again for the histogram.  Elements whose column
         value is not finite and positive are left out (``n`` counts the rest)."""
         torch = self.torch
-        pb = self.problem
-        T, S = pb.n_times, pb.n_states
-        theta_t = theta if isinstance(theta, torch.Tensor) else np.asarray(theta)
-        W = int(theta_t.shape[1])
-        if W < 1:
-            raise ValueError("band needs at least one walker")
-        y0 = self._dev(y0, (S, W))
-        theta = self._dev(theta, (pb.n_params, W))
+        T, S = self.problem.n_times, self.problem.n_states
+        W, y0, theta, spans, buf, status = self._posterior_begin("band", y0, theta, chunk)
         masks = np.asarray([1 << s for s in range(S)] if col_masks is None else col_masks, dtype=np.uint64)
         q = np.ascontiguousarray(np.asarray(quantiles, dtype=np.float64).reshape(-1))
         n_cols, n_q = len(masks), len(q)
-        spans, buf = self._chunk_spans(W, chunk)
         acc = torch.empty((T, n_cols, 5), dtype=torch.float64, device=self.dev)
         hist = torch.empty((T, n_cols, int(n_bins)), dtype=torch.int32, device=self.dev)
         out = torch.empty((n_q, T, n_cols), dtype=torch.float64, device=self.dev)
-        st_or = torch.zeros((), dtype=torch.int32, device=self.dev)
-        st_n = torch.zeros((), dtype=torch.int64, device=self.dev)
-        self._sync_stream()
         self.ctx.band_begin(masks, n_bins, _ptr(acc), _ptr(hist))
 
         def run(a, b, first):
-            return self._run_span(y0, theta, spans, buf, a, b, nt_stores, (st_or, st_n) if first else None)
+            return self._run_span(y0, theta, spans, buf, a, b, nt_stores, status if first else None)
 
         for a, b in spans:
             w, traj = run(a, b, True)
@@ -404,9 +420,7 @@ class Engine:
         torch.cuda.synchronize(self.dev)
         res = band_summary(acc.cpu().numpy())
         res["q"] = out.cpu().numpy()
-        res["status_or"] = int(st_or.item())
-        res["n_status"] = int(st_n.item())
-        return res
+        return self._status_result(res, status)
 
     # -- posterior-wide model comparison -----------------------------------------------------------
     def waic(self, y0, theta, chunk=None, terms: bool = False, nt_stores: bool = True):
@@ -424,25 +438,16 @@ class Engine:
         term (NaN where it is not finite)."""
         torch = self.torch
         pb = self.problem
-        theta_t = theta if isinstance(theta, torch.Tensor) else np.asarray(theta)
-        W = int(theta_t.shape[1])
-        if W < 1:
-            raise ValueError("waic needs at least one walker")
         if pb.n_obs < 1:
             raise ValueError("waic needs a problem with observations")
-        y0 = self._dev(y0, (pb.n_states, W))
-        theta = self._dev(theta, (pb.n_params, W))
-        spans, buf = self._chunk_spans(W, chunk)
+        W, y0, theta, spans, buf, status = self._posterior_begin("waic", y0, theta, chunk)
         acc = torch.empty((pb.n_obs, N.WAIC_ACC), dtype=torch.float64, device=self.dev)
         point = torch.empty((pb.n_obs, len(N.WAIC_POINT_FIELDS)), dtype=torch.float64, device=self.dev)
         summary = torch.empty(len(N.WAIC_SUMMARY_FIELDS), dtype=torch.float64, device=self.dev)
         terms_t = torch.empty((pb.n_obs, W), dtype=torch.float64, device=self.dev) if terms else None
-        st_or = torch.zeros((), dtype=torch.int32, device=self.dev)
-        st_n = torch.zeros((), dtype=torch.int64, device=self.dev)
-        self._sync_stream()
         self.ctx.waic_begin(_ptr(acc))
         for a, b in spans:
-            w, traj = self._run_span(y0, theta, spans, buf, a, b, nt_stores, (st_or, st_n))
+            w, traj = self._run_span(y0, theta, spans, buf, a, b, nt_stores, status)
             self.ctx.waic_accum(w, _ptr(traj), _ptr(acc), _ptr(terms_t), W if terms else 0, a, N.OE_ASYNC)
         self.ctx.waic_finish(_ptr(acc), _ptr(point), _ptr(summary), N.OE_ASYNC)
         torch.cuda.synchronize(self.dev)
@@ -451,8 +456,7 @@ class Engine:
         res["n"] = res["n"].astype(np.int64)
         sm = summary.cpu().numpy()
         res["summary"] = {name: float(sm[k]) for k, name in enumerate(N.WAIC_SUMMARY_FIELDS)}
-        res["status_or"] = int(st_or.item())
-        res["n_status"] = int(st_n.item())
+        self._status_result(res, status)
         if terms:
             res["terms"] = terms_t
         return res

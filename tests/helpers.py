@@ -1,5 +1,9 @@
 """Shared test helpers: the demo models/priors exactly as the notebook declares them."""
+import functools
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
 import pandas as pd
@@ -106,3 +110,44 @@ def chain_problem(n, method="rk4", substeps=1, T=1000, ode=None, device_model="c
                        rk4_substeps=substeps, device_model=device_model,
                        **{p: parameter(init_value=v) for p, v in th.items()}, **kw)
     return m
+
+
+_AUX_FIELDS = {"VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
+               "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
+
+
+@functools.lru_cache(maxsize=None)
+def aux_kernel_resources():
+    """{mangled kernel name: resources} of inst_aux.hip from the compiler's resource remarks,
+    compiled (once per session) as tests/test_kernel_resources.py compiles the model units; None
+    without hipcc."""
+    from test_kernel_resources import CSRC, FLAGS, HIPCC
+    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+        return None
+    r = subprocess.run([HIPCC, *FLAGS, "inst_aux.hip"], cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:]
+    kernels, cur = {}, None
+    for line in r.stdout.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = kernels.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark:\s+([^:]+): (\d+)", line)
+        if m and cur is not None and m.group(1).strip() in _AUX_FIELDS:
+            cur[_AUX_FIELDS[m.group(1).strip()]] = int(m.group(2))
+    return kernels
+
+
+def run_plan_driver(name, tmp_dir):
+    """tests/sanitize/<name>_plan_driver.cpp built with ASan + UBSan into tmp_dir and run as a
+    stand-alone program: its output."""
+    exe = os.path.join(str(tmp_dir), f"{name}_plan_asan")
+    src = os.path.join(ROOT, "tests", "sanitize", f"{name}_plan_driver.cpp")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fno-omit-frame-pointer",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "SANITIZE OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+    return r.stdout

@@ -2,37 +2,19 @@
 compiler (CPU, no GPU): inst_aux.hip compiled as tests/test_kernel_resources.py compiles the
 model units.  The kernels loop over the columns and hold one column's accumulators /
 histogram at a time, so none of this depends on the column count."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-from test_kernel_resources import CSRC, FLAGS, HIPCC
+from helpers import aux_kernel_resources
 
-_FIELDS = {"VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
-           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 WORKGROUP_LDS = 64 * 1024  # bytes a workgroup may allocate
 MAX_BINS = 4096            # oe_band_begin's largest n_bins
 
 
 @pytest.fixture(scope="module")
 def aux():
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+    kernels = aux_kernel_resources()
+    if kernels is None:
         pytest.skip("hipcc not available")
-    r = subprocess.run([HIPCC, *FLAGS, "inst_aux.hip"], cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:]
-    kernels, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([^:]+): (\d+)", line)
-        if m and cur is not None and m.group(1).strip() in _FIELDS:
-            cur[_FIELDS[m.group(1).strip()]] = int(m.group(2))
     return kernels
 
 

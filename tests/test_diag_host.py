@@ -3,13 +3,12 @@ launch plan under ASan + UBSan (a stand-alone program), the posterior DataFrame 
 mapping, and the missing-device error."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 
-from helpers import ROOT, product_model
+from helpers import ROOT, product_model, run_plan_driver
 from odelib_amd import _native as N
 from odelib_amd.Framework import diag_inputs
 
@@ -39,15 +38,7 @@ def test_diag_run_without_a_context_is_a_code_not_a_crash():
 
 @pytest.fixture(scope="module")
 def plan_driver_output(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("diag_plan") / "diag_plan_asan")
-    src = os.path.join(ROOT, "tests", "sanitize", "diag_plan_driver.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fno-omit-frame-pointer",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SANITIZE OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
-    return r.stdout
+    return run_plan_driver("diag", tmp_path_factory.mktemp("diag_plan"))
 
 
 def test_diag_plan_under_asan_ubsan(plan_driver_output):

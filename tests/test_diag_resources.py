@@ -2,37 +2,19 @@
 compiler (CPU, no GPU): inst_aux.hip compiled as tests/test_band_resources.py compiles it.
 k_diag_acov keeps LB = 16 lag accumulators and a window of 16 delayed draws per lane in
 registers, indexed by unrolled constants only: any dynamic index would show as scratch."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-from test_kernel_resources import CSRC, FLAGS, HIPCC
+from helpers import aux_kernel_resources
 
-_FIELDS = {"VGPRs": "vgpr", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
-           "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds"}
 WORKGROUP_LDS = 64 * 1024  # bytes a workgroup may allocate
 KERNELS = ("k_diag_moments", "k_diag_merge", "k_diag_acov", "k_diag_eval")
 
 
 @pytest.fixture(scope="module")
 def diag():
-    if not os.path.exists(HIPCC) and shutil.which("hipcc") is None:
+    kernels = aux_kernel_resources()
+    if kernels is None:
         pytest.skip("hipcc not available")
-    r = subprocess.run([HIPCC, *FLAGS, "inst_aux.hip"], cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:]
-    kernels, cur = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([^:]+): (\d+)", line)
-        if m and cur is not None and m.group(1).strip() in _FIELDS:
-            cur[_FIELDS[m.group(1).strip()]] = int(m.group(2))
     return {k: v for k, v in kernels.items() if "k_diag_" in k}
 
 

@@ -186,6 +186,22 @@ def test_reduce_kernels_on_synthetic_trajectories(eng5, W):
         assert np.isnan(res["q"][:, 4, 1]).all() and res["n"][4, 1] == 0
 
 
+@pytest.mark.parametrize("W", [65, 4097])
+def test_moments_are_the_same_bits_run_to_run(eng5, W):
+    """two calls on the same chunk: mean and M2 bit for bit (NaN cells compared as bits too)"""
+    traj = eng5.torch.as_tensor(synthetic(W), device=eng5.dev).contiguous()
+
+    def run():
+        band = Band(eng5, 64)
+        band.moments(traj)
+        acc = band.acc.cpu().numpy()
+        return acc[..., 1].copy(), acc[..., 2].copy()
+
+    (mean_a, m2_a), (mean_b, m2_b) = run(), run()
+    assert np.array_equal(mean_a.view(np.uint64), mean_b.view(np.uint64))
+    assert np.array_equal(m2_a.view(np.uint64), m2_b.view(np.uint64))
+
+
 def test_chunk_invariance_of_the_kernels(eng5):
     W = 4097
     host = synthetic(W)

@@ -5,13 +5,12 @@ reference, which pins the formulas the kernels use before any GPU run."""
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 
-from helpers import ROOT
+from helpers import ROOT, run_plan_driver
 import odelib_amd
 from odelib_amd import _native as N
 
@@ -53,15 +52,7 @@ def test_without_a_context_each_call_is_a_code_not_a_crash():
 # ------------------------------------------------------------------ the launch plan
 @pytest.fixture(scope="module")
 def plan_driver_output(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("waic_plan") / "waic_plan_asan")
-    src = os.path.join(ROOT, "tests", "sanitize", "waic_plan_driver.cpp")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fno-omit-frame-pointer",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src], check=True)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SANITIZE OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
-    return r.stdout
+    return run_plan_driver("waic", tmp_path_factory.mktemp("waic_plan"))
 
 
 def test_waic_plan_under_asan_ubsan(plan_driver_output):
@@ -128,7 +119,7 @@ EMPTY = (0.0, 0.0, 0.0, -np.inf, 0.0)
 
 
 def push(c, e):
-    """waic.cuh lse_push, operation for operation"""
+    """waic.cuh Lse::push, operation for operation"""
     n, mean, m2, a, s = c
     n = n + 1.0
     d = e - mean
@@ -143,7 +134,7 @@ def push(c, e):
 
 
 def merge(A, B):
-    """waic.cuh lse_merge: Chan for the moments, the sums rescaled to the larger maximum; an empty
+    """waic.cuh merge(Lse, Lse): Chan for the moments, the sums rescaled to the larger maximum; an empty
     side leaves the other's bits, and -inf - (-inf) is never formed"""
     if B[0] == 0.0:
         return A

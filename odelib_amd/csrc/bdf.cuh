@@ -419,17 +419,9 @@ __device__ __forceinline__ void bdfl_observe(const DevProblem& pb, BdfLane<S, LD
   const Obs* obs = pb.obs;
   const int i = st.nxt;
   int k = st.k;
-  while (k < pb.n_obs && obs[k].tidx == i) {
-    const uint64_t mask = obs[k].mask;
-    double c = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-      if ((mask >> s) & 1ull) c = c + yo[s];
-    oc.c[(int64_t)k * oc.ld + oc.col] = c;
-    ++k;
-  }
+  for (; k < pb.n_obs && obs[k].tidx == i; ++k) oc.c[(int64_t)k * oc.ld + oc.col] = masked_sum(yo, obs[k].mask);
   st.k = k;
-  st.nxt = (k < pb.n_obs) ? obs[k].tidx : 0x7fffffff;
+  st.nxt = next_observed(pb, obs, k);
 }
 
 // the backward-difference interpolant of the step just accepted (order Q, ending at tn) at ti
@@ -710,7 +702,7 @@ __device__ __forceinline__ void integrate_bdf_lane(const DevProblem& pb, double 
   st.t = t;
   st.i = i;
   st.k = k;
-  st.nxt = (k < pb.n_obs) ? pb.obs[k].tidx : 0x7fffffff;
+  st.nxt = next_observed(pb, pb.obs, k);
 #pragma unroll
   for (int j = 0; j < kWin; ++j) st.wv[j] = pb.times[i + j];
   st.nst = 0;
@@ -794,13 +786,7 @@ __device__ __forceinline__ void integrate_bdf_lane(const DevProblem& pb, double 
     for (int kk = (int)kmin; kk < pb.n_obs; ++kk) {
       const bool in = part && kk >= k_first && kk < st.k;
       const double c = in ? oc.c[(int64_t)kk * oc.ld + oc.col] : 1.0;
-      const double O = obs[kk].O, two_s2 = obs[kk].two_s2, O_lin = obs[kk].O_lin;
-      const double dd = O - oe_log(c);
-      const double term = (dd * dd) / two_s2;
-      if (in && __builtin_isfinite(term)) { a.chi += term; a.nvalid += 1; }
-      const double r = c - O_lin;
-      const double r2 = r * r;
-      if (in && !__builtin_isnan(r2)) a.ssres += r2;
+      fold_obs(obs_term(obs + kk), c, a, in);
     }
   }
   if (part) check_finite(y, a);

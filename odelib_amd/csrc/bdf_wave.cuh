@@ -100,22 +100,12 @@ __device__ __forceinline__ void observe_lane(const DevProblem& pb, int i, const 
                                              Acc& a) {
   const Obs* obs = pb.obs;
   check_finite(y, a);
-  while (k < pb.n_obs && obs[k].tidx == i) {
+  for (; k < pb.n_obs && obs[k].tidx == i; ++k) {
     const uint64_t mask = obs[k].mask;
-    const double O = obs[k].O, two_s2 = obs[k].two_s2, O_lin = obs[k].O_lin;
-    double c = 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s)
-      if ((mask >> s) & 1ull) c = c + y[s];
-    const double d = O - oe_log(c);
-    const double term = (d * d) / two_s2;
-    if (__builtin_isfinite(term)) { a.chi += term; a.nvalid += 1; }
-    const double r = c - O_lin;
-    const double r2 = r * r;
-    if (!__builtin_isnan(r2)) a.ssres += r2;
-    ++k;
+    const ObsTerm rec = obs_term(obs + k);
+    fold_obs(rec, masked_sum(y, mask), a);
   }
-  nxt = (k < pb.n_obs) ? obs[k].tidx : 0x7fffffff;
+  nxt = next_observed(pb, obs, k);
 }
 
 // Output of one lane at its own grid index i (trajectory row store + minimum + observations):
@@ -450,7 +440,7 @@ __device__ __forceinline__ void integrate_bdf(const DevProblem& pb, double (&y)[
   st.i = i;
   st.k = k;
   st.ti = pb.times[i];
-  st.nxt = (k < pb.n_obs) ? pb.obs[k].tidx : 0x7fffffff;
+  st.nxt = next_observed(pb, pb.obs, k);
   st.nst = 0;
   {
     double f[S];

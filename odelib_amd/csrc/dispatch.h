@@ -47,12 +47,12 @@ struct Entry {
   // BDF kernel, [beside][traj][nt] (after the DOPRI5 kernel: its difference table in registers)
   Kernel integrate_hq[2][2][2];
   Kernel bdf_hq[2][2][2];  // [beside][traj][nt]
-  Kernel mh[kMethods];
+  Kernel mh[kMethods];       // Metropolis–Hastings (mh.cuh), one lane per chain
   Kernel mh_init[kMethods];  // the a-priori pass (MHArgs::init)
   Kernel mh_tree[kMethods];  // speculative MH rounds (k_mh_tree); the resolve kernel is shared
   Kernel stiff_wave[2][2];   // [traj][nt]: S > kStiffRegS stiff redo, one wave per walker
   Kernel dopri5_split[2][2];  // [traj][nt]: DOPRI5 with split_lanes lanes per walker (split.cuh)
-  Kernel mh_split;            // DOPRI5 Metropolis–Hastings, split_lanes lanes per walker
+  Kernel mh_split;            // DOPRI5 Metropolis–Hastings, split_lanes lanes per walker (mh.cuh)
   Kernel mh_split_tree;       // its speculative rounds (k_mh_split_tree)
   int32_t split_lanes = 0;    // 0: the model has no split kernel
 };

@@ -33,8 +33,8 @@ __global__ void __launch_bounds__(256) k_philox_draws(const oe::DrawArgs d) {
   oe::philox_draw_iteration(d, g - k * d.W, d.it0 + (int)k);
 }
 
-// k_mh_tree's resolution: one lane per chain walks its tree with k_mh's accept test and
-// bookkeeping, iteration by iteration, in the reference's arithmetic (Samplers.py:124-153)
+// k_mh_tree's resolution: one lane per chain walks its tree with mh.cuh's chain step (k_mh's
+// accept test and bookkeeping), iteration by iteration, in the reference's arithmetic (Samplers.py:124-153)
 __global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, const oe::MHTreeArgs ta, int32_t S) {
   using namespace oe;
   constexpr int kMaxD = 16;  // oe_mh_run caps the depth
@@ -46,13 +46,12 @@ __global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, con
   const int PS = P + 5;
   const int D = ta.depth;
   const uint32_t off = (uint32_t)w * 8u;
-  double* cur = ma.cur;
-  double chi = Row(cur, W).ld(off), rsq = Row(cur + W, W).ld(off), aic = Row(cur + 2 * W, W).ld(off);
-  double nacc = Row(cur + 3 * W, W).ld(off);
+  ChainPoint pt = load_point(ma.cur, W, RowLd{W, off});
   // 1. the decisions.  The only loads on the path's dependency chain are the node chis; the
   //    next level's two candidates are loaded before each decision, the uniforms up front.
-  //    exp/log inline (the same ocml functions k_mh calls out of line: the same bits).
-  double uj[kMaxD], cj[kMaxD], rj[kMaxD], aj[kMaxD], nj[kMaxD];
+  //    mh_accepts<true>: exp/log inline (the same ocml functions k_mh calls out of line: the same bits).
+  double uj[kMaxD];
+  ChainPoint pj[kMaxD];  // the chain point after iteration j
   int32_t keep[kMaxD];  // node holding the chain's parameters after iteration j (-1: the round's start)
 #pragma unroll
   for (int j = 0; j < kMaxD; ++j)
@@ -70,20 +69,12 @@ __global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, con
       c0 = ta.node_chi[n0 * W + w];
       c1 = ta.node_chi[(n0 + (int64_t)(1u << j)) * W + w];
     }
-    const double lr = exp(chi - chin);
-    const double accp = exp(log(lr));
-    const bool acc = accp > uj[j];
+    const bool acc = mh_accepts<true>(pt.chi, chin, uj[j]);
     if (acc) {
-      chi = chin;
-      rsq = 1.0 - ta.node_ss[n * W + w] / pb.sstot;
-      aic = -2.0 * (-chi) + 2.0 * (double)pb.pnum;
-      nacc += 1.0;
+      pt = chain_point(chin, ta.node_ss[n * W + w], pt.nacc + 1.0, pb);
       last = (int32_t)n;
     }
-    cj[j] = chi;
-    rj[j] = rsq;
-    aj[j] = aic;
-    nj[j] = nacc;
+    pj[j] = pt;
     keep[j] = last;
     path |= (acc ? 1u : 0u) << j;
     chin = acc ? c1 : c0;
@@ -96,31 +87,12 @@ __global__ void __launch_bounds__(256) k_mh_resolve(const oe::DevProblem pb, con
     if (j >= D || it <= ma.burnin) continue;
     const double* src = keep[j] >= 0 ? ta.node_th + (int64_t)keep[j] * P * W : ma.theta;
     double* row = ma.samples + (int64_t)(it - ma.row0) * PS * W;
-    for (int q = 0; q < P; ++q) Row(row + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
-    Row(row + (int64_t)P * W, W).st(off, cj[j]);
-    Row(row + (int64_t)(P + 1) * W, W).st(off, rj[j]);
-    Row(row + (int64_t)(P + 2) * W, W).st(off, aj[j]);
-    Row(row + (int64_t)(P + 3) * W, W).st(off, (double)it);
-    Row(row + (int64_t)(P + 4) * W, W).st(off, nj[j] / (double)it);
+    copy_rows(row, src, P, W, off);
+    store_sample_tail(row, P, W, off, pj[j], it);
   }
-  if (last >= 0) {
-    const double* src = ta.node_th + (int64_t)last * P * W;
-    for (int q = 0; q < P; ++q) Row(ma.theta + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
-    if (ma.status) ma.status[w] = ta.node_st[(int64_t)last * W + w];
-  }
-  // linked initial states follow the current parameters (k_mh stores them every iteration:
-  // the same final values)
-  if (ma.any_walk) {
-    const double* src = last >= 0 ? ta.node_th + (int64_t)last * P * W : ma.theta;
-    for (int s = 0; s < S; ++s) {
-      const int pi = ma.init_param[s];
-      if (pi >= 0) Row(ma.y0 + (int64_t)s * W, W).st(off, Row(src + (int64_t)pi * W, W).ld(off));
-    }
-  }
-  Row(cur, W).st(off, chi);
-  Row(cur + W, W).st(off, rsq);
-  Row(cur + 2 * W, W).st(off, aic);
-  Row(cur + 3 * W, W).st(off, nacc);
+  if (last >= 0 && ma.status) ma.status[w] = ta.node_st[(int64_t)last * W + w];
+  keep_node_state(ta, P, S, last, off);
+  store_point(ma.cur, W, off, pt);
 }
 
 // The same resolution with one wave per chain, for trees of up to 4 095 nodes (depth <= 12):
@@ -131,7 +103,8 @@ __global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb,
   using namespace oe;
   constexpr int kMaxD = kResolveLdsDepth;
   __shared__ double s_chi[(1 << kMaxD) - 1];
-  __shared__ double s_u[kMaxD], s_c[kMaxD], s_r[kMaxD], s_a[kMaxD], s_n[kMaxD];
+  __shared__ double s_u[kMaxD];
+  __shared__ ChainPoint s_pt[kMaxD];
   __shared__ int32_t s_keep[kMaxD];
   __shared__ int32_t s_last;
   const MHArgs& ma = ta.m;
@@ -147,36 +120,23 @@ __global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb,
   if (t < D) s_u[t] = Row(ma.u + (int64_t)(ma.it0 + t - ma.draw_it0) * W, W).ld(off);
   __syncthreads();
   if (t == 0) {
-    double* cur = ma.cur;
-    double chi = Row(cur, W).ld(off), rsq = Row(cur + W, W).ld(off), aic = Row(cur + 2 * W, W).ld(off);
-    double nacc = Row(cur + 3 * W, W).ld(off);
+    ChainPoint pt = load_point(ma.cur, W, RowLd{W, off});
     uint32_t path = 0;
     int32_t last = -1;
     for (int j = 0; j < D; ++j) {
       const int n = (1 << j) - 1 + (int)path;
       const double chin = s_chi[n];
-      const double lr = exp(chi - chin);
-      const double accp = exp(log(lr));
-      const bool acc = accp > s_u[j];
+      const bool acc = mh_accepts<true>(pt.chi, chin, s_u[j]);
       if (acc) {
-        chi = chin;
-        rsq = 1.0 - ta.node_ss[(int64_t)n * W + w] / pb.sstot;
-        aic = -2.0 * (-chi) + 2.0 * (double)pb.pnum;
-        nacc += 1.0;
+        pt = chain_point(chin, ta.node_ss[(int64_t)n * W + w], pt.nacc + 1.0, pb);
         last = n;
       }
-      s_c[j] = chi;
-      s_r[j] = rsq;
-      s_a[j] = aic;
-      s_n[j] = nacc;
+      s_pt[j] = pt;
       s_keep[j] = last;
       path |= (acc ? 1u : 0u) << j;
     }
     s_last = last;
-    Row(cur, W).st(off, chi);
-    Row(cur + W, W).st(off, rsq);
-    Row(cur + 2 * W, W).st(off, aic);
-    Row(cur + 3 * W, W).st(off, nacc);
+    store_point(ma.cur, W, off, pt);
     if (last >= 0 && ma.status) ma.status[w] = ta.node_st[(int64_t)last * W + w];
   }
   __syncthreads();
@@ -186,29 +146,12 @@ __global__ void __launch_bounds__(64) k_mh_resolve_wave(const oe::DevProblem pb,
       const int k = s_keep[t];
       const double* src = k >= 0 ? ta.node_th + (int64_t)k * P * W : ma.theta;
       double* row = ma.samples + (int64_t)(it - ma.row0) * PS * W;
-      for (int q = 0; q < P; ++q) Row(row + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
-      Row(row + (int64_t)P * W, W).st(off, s_c[t]);
-      Row(row + (int64_t)(P + 1) * W, W).st(off, s_r[t]);
-      Row(row + (int64_t)(P + 2) * W, W).st(off, s_a[t]);
-      Row(row + (int64_t)(P + 3) * W, W).st(off, (double)it);
-      Row(row + (int64_t)(P + 4) * W, W).st(off, s_n[t] / (double)it);
+      copy_rows(row, src, P, W, off);
+      store_sample_tail(row, P, W, off, s_pt[t], it);
     }
   }
   __syncthreads();
-  if (t == 0) {
-    const int32_t last = s_last;
-    if (last >= 0) {
-      const double* src = ta.node_th + (int64_t)last * P * W;
-      for (int q = 0; q < P; ++q) Row(ma.theta + (int64_t)q * W, W).st(off, Row(src + (int64_t)q * W, W).ld(off));
-    }
-    if (ma.any_walk) {
-      const double* src = last >= 0 ? ta.node_th + (int64_t)last * P * W : ma.theta;
-      for (int s = 0; s < S; ++s) {
-        const int pi = ma.init_param[s];
-        if (pi >= 0) Row(ma.y0 + (int64_t)s * W, W).st(off, Row(src + (int64_t)pi * W, W).ld(off));
-      }
-    }
-  }
+  if (t == 0) keep_node_state(ta, P, S, s_last, off);
 }
 
 // posterior predictive bands: the reductions across walkers (band.cuh)

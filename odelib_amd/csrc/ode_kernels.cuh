@@ -1,5 +1,6 @@
-// ode_kernels.cuh — batched ODE integration + fused likelihood + Metropolis–Hastings
-// for MI355X (gfx950).  Header-only templates over a Model (models.cuh).
+// ode_kernels.cuh — batched ODE integration + fused likelihood for MI355X (gfx950): the problem
+// description, the likelihood term, RK4, lockstep DOPRI5, the integrate kernels.  Header-only
+// templates over a Model (models.cuh); Metropolis–Hastings is mh.cuh, included last.
 //
 // Execution model:
 //   * one lane = one walker; state y[S], parameters θ[P] and RK stages live in VGPRs;
@@ -282,6 +283,44 @@ __device__ __forceinline__ void store_row(int i, const double (&y)[S], double* _
   store_row_at<S, TRAJ, NT>(TRAJ ? traj + (int64_t)i * S * W : nullptr, y, W, off, active, a);
 }
 
+// ---- the likelihood term of one observation record, stated once.  The record
+// pointer (constant address space or plain) and the place of its loads (obs_term) are the caller's.
+struct ObsTerm { double O, two_s2, O_lin; };  // what the term reads of a record
+template <class ObsPtr>
+__device__ __forceinline__ ObsTerm obs_term(ObsPtr rec) {
+  return ObsTerm{rec->O, rec->two_s2, rec->O_lin};
+}
+// C: the masked states of a lane, from 0.0 in increasing state order, as numpy's sum
+template <int S>
+__device__ __forceinline__ double masked_sum(const double (&y)[S], uint64_t mask) {
+  double c = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+    if ((mask >> s) & 1ull) c = c + y[s];
+  return c;
+}
+// chi term, in the operation order of stats.py:41
+template <bool INLINE_LOG = false>
+__device__ __forceinline__ double chi_term(const ObsTerm& t, double c) {
+  const double d = t.O - (INLINE_LOG ? log(c) : oe_log(c));
+  return (d * d) / t.two_s2;
+}
+// the term, counted if finite, and the R² residual (stats.py:52: np.nansum skips NaN only) into
+// the accumulators of a lane that takes part (`in`: uniform control flow for the others)
+template <bool INLINE_LOG = false>
+__device__ __forceinline__ void fold_obs(const ObsTerm& t, double c, Acc& a, bool in = true) {
+  const double term = chi_term<INLINE_LOG>(t, c);
+  if (in && __builtin_isfinite(term)) { a.chi += term; a.nvalid += 1; }
+  const double r = c - t.O_lin;
+  const double r2 = r * r;
+  if (in && !__builtin_isnan(r2)) a.ssres += r2;
+}
+// grid index of record k, the next observed one, or past every grid when there is none
+template <class ObsPtr>
+__device__ __forceinline__ int next_observed(const DevProblem& pb, ObsPtr obs, int k) {
+  return (k < pb.n_obs) ? obs[k].tidx : 0x7fffffff;
+}
+
 // Fold every observation recorded at grid index i into the likelihood (caller knows
 // one exists or checks `k`).  Finiteness is checked here and at the final state
 // (NaN/inf propagate through the RHS), not at every step.
@@ -290,22 +329,17 @@ __device__ __forceinline__ void observe(const DevProblem& pb, int i, const doubl
   const cptr<Obs> obs = kconst(pb.obs);
   if (!(k < pb.n_obs && obs[k].tidx == i)) return;
   check_finite(y, a);
-  while (k < pb.n_obs && obs[k].tidx == i) {
+  for (; k < pb.n_obs && obs[k].tidx == i; ++k) {
     const uint64_t mask = obs[k].mask;
-    const double O = obs[k].O, two_s2 = obs[k].two_s2, O_lin = obs[k].O_lin;
+    const ObsTerm rec = obs_term(obs + k);
+    // masked_sum(y, mask) on this site's own text: called here, the lockstep DOPRI5 kernels of
+    // the wide chains gain spills (k_integrate<Chain<20>, dopri5> scratch 0 -> 16 B/lane,
+    // <Chain<12>, dopri5, traj> 6 -> 8 spilled VGPRs, <Chain<24>, dopri5> 132 -> 134)
     double c = 0.0;
 #pragma unroll
     for (int s = 0; s < S; ++s)
-      if ((mask >> s) & 1ull) c = c + y[s];  // increasing state order, as numpy's sum
-    // chi term, in the operation order of stats.py:41
-    const double d = O - (INLINE_LOG ? log(c) : oe_log(c));
-    const double term = (d * d) / two_s2;
-    if (__builtin_isfinite(term)) { a.chi += term; a.nvalid += 1; }
-    // R² residual (stats.py:52 np.nansum skips NaN only)
-    const double r = c - O_lin;
-    const double r2 = r * r;
-    if (!__builtin_isnan(r2)) a.ssres += r2;
-    ++k;
+      if ((mask >> s) & 1ull) c = c + y[s];
+    fold_obs<INLINE_LOG>(rec, c, a);
   }
 }
 
@@ -316,7 +350,7 @@ __device__ __forceinline__ void observe_next(const DevProblem& pb, int i, const 
                                              int& nxt, Acc& a) {
   if (i != nxt) return;
   observe<S>(pb, i, y, k, a);
-  nxt = (k < pb.n_obs) ? kconst(pb.obs)[k].tidx : 0x7fffffff;
+  nxt = next_observed(pb, kconst(pb.obs), k);
 }
 
 // Emit grid point i: row store + minimum + observations.
@@ -805,7 +839,7 @@ __device__ __forceinline__ bool integrate_dopri5(const DevProblem& pb, double (&
   // row i of the trajectory, advanced with i (no 64-bit multiply per emitted row)
   double* trow = TRAJ ? traj + (int64_t)S * W : nullptr;
   const cptr<double> fifth = kconst(kFifthScale.v);
-  int nxt = (k < pb.n_obs) ? kconst(pb.obs)[k].tidx : 0x7fffffff;  // next observed index
+  int nxt = next_observed(pb, kconst(pb.obs), k);
   double t_obs = (nxt < pb.T) ? times[nxt] : __builtin_inf();        // and its time
   int nst = 0;  // steps since the last grid point
   bool last_rej = false;
@@ -1644,425 +1678,7 @@ __global__ void __launch_bounds__(256 + 64 * NSW) k_integrate_rk4_piped(const De
   }
 }
 
-// ---------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11) counter-based RNG for the MH proposals.
-// ---------------------------------------------------------------------------------
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    c = U4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1,
-           (uint32_t)p0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-// 53-bit uniform in [0,1) from two words (numpy random_sample construction)
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-  return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-}
-
-// Proposal draws of iterations [it0, it1) for every walker, in the layout of the
-// replay streams: dz[it - it0][p][w] = step_sd * N(0,1), u[it - it0][w] = U[0,1).
-// Counter (global walker id, iteration, pair index) under key = seed, so the draws do
-// not depend on how walkers are sharded or iterations chunked.  Its own kernel, so the
-// MH kernel carries no Box–Muller transcendentals (register pressure).
-struct DrawArgs {
-  int64_t W;
-  int64_t walker_offset;
-  int32_t it0, it1;
-  int32_t P;
-  uint32_t seed_lo, seed_hi;
-  double step_sd;
-  double* dz;  // [it1 - it0][P][W]
-  double* u;   // [it1 - it0][W]
-};
-
-__device__ __forceinline__ void philox_draw_iteration(const DrawArgs d, int64_t w, int it) {
-  const uint64_t gid = (uint64_t)(d.walker_offset + w);
-  const int64_t W = d.W;
-  {
-    double* dz = d.dz + (int64_t)(it - d.it0) * d.P * W + w;
-    for (int j = 0; j < d.P; j += 2) {
-      const U4 r = philox4x32_10(U4{(uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)it, (uint32_t)(j >> 1)},
-                                 d.seed_lo, d.seed_hi);
-      const double u1 = 1.0 - u53(r.x, r.y);
-      const double u2 = u53(r.z, r.w);
-      const double rad = sqrt(-2.0 * log(u1));
-      const double ang = 6.283185307179586 * u2;
-      dz[(int64_t)j * W] = d.step_sd * (rad * cos(ang));
-      if (j + 1 < d.P) dz[(int64_t)(j + 1) * W] = d.step_sd * (rad * sin(ang));
-    }
-    const U4 r = philox4x32_10(U4{(uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)it, 0x80000000u},
-                               d.seed_lo, d.seed_hi);
-    d.u[(int64_t)(it - d.it0) * W + w] = u53(r.x, r.y);
-  }
-}
-
-// ---------------------------------------------------------------------------------
-// Kernel 2: Metropolis–Hastings, iterations [it0, it1) for every walker
-// (Samplers.py:104-153).  One lane = one chain; the chain state lives in HBM
-// between chunked launches.
-// ---------------------------------------------------------------------------------
-struct MHArgs {
-  int64_t W;
-  int64_t walker_offset;
-  int32_t it0, it1;        // iteration range of this launch (1-based, ref `it`)
-  int32_t burnin;
-  int32_t row0;            // iteration stored in samples row 0 (burnin+1, or later on resume)
-  int32_t draw_it0;        // iteration whose draws sit at offset 0 of dz/u
-  int32_t init;            // 1: compute the a-priori chi/R²/AIC only (Samplers.py:88-91)
-  int32_t any_walk;
-  uint64_t walk_mask;      // bit p: parameter p walks
-  int32_t init_param[64];  // per state: -1 or parameter index
-  const double* dz;        // [..][P][W] step_sd·N(0,1) (replay streams or philox_draws)
-  const double* u;         // [..][W]
-  double* theta;           // [P][W]
-  double* y0;              // [S][W]
-  double* samples;         // [kept][P+5][W]
-  double* cur;             // [4][W]: chi, rsquared, aic, n_accepted
-  int32_t* status;         // [W]
-  int32_t n_rows;          // rows of samples (the kept iterations of this call)
-};
-
-// Integrity checks of the MH kernel's uniform state (below): compiled into the debug
-// library (make debug -> libodelib_amd_debug.so), whose MH parity run is a GPU test.
-// Off in the product library: even these few scalar compares move the register
-// allocation of the chain20 DOPRI5 MH kernel (scratch 176 -> 240 B/lane).
-#ifndef OE_MH_CHECKS
-#define OE_MH_CHECKS 0
-#endif
-
-// Element w of a walker-minor row [W] through a buffer resource: row base and size in
-// SGPRs, the lane's byte offset w*8 in one VGPR.  With plain pointers the compiler
-// forms one 64-bit per-lane address per row, and since every row base is invariant in
-// the MH iteration loop it hoists them: two VGPRs per row, dozens of rows — the
-// register cost of a second wave per SIMD.
-struct Row {
-  __amdgpu_buffer_rsrc_t r;
-  __device__ __forceinline__ Row(const double* row, int64_t W)
-      // num_records is 32 bits: W = 2^29 (the ABI maximum) makes W*8 = 2^32, clamp it
-      : r(__builtin_amdgcn_make_buffer_rsrc((void*)row, 0,
-                                            (int)(uint32_t)(W * 8 > 0xffffffffll ? 0xffffffffll : W * 8),
-                                            0x00020000)) {}
-  __device__ __forceinline__ double ld(uint32_t off) const {
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-  }
-  __device__ __forceinline__ void st(uint32_t off, double v) const {
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, off, 0, 0);
-  }
-};
-
-// A uniform pointer the compiler must treat as redefined here: row resources derived
-// from it are rebuilt at their use (a few SALU) instead of hoisted out of the MH
-// iteration loop, where S + 2P hoisted 4-SGPR descriptors (chain20: ~120 SGPRs) stay
-// live across the whole integration and spill to VGPR lanes.
-template <class T>
-__device__ __forceinline__ T* opaque(T* p) {
-  asm volatile("" : "+s"(p));
-  return p;
-}
-// The same for a wave-uniform scalar (a kernel argument): the predicates the MH iteration
-// derives from it — j < P, walk bit j, init_param[s] == j per state and parameter (the
-// '<state>0' picks) — are formed at their use in each iteration instead of hoisted out of
-// the iteration loop as 64-bit lane masks, ~50 of which lived across the whole integration
-// in SGPR pairs spilled to VGPR lanes (k_mh<TwoI, auto>: 510 SGPRs spilled).
-#ifndef OE_MH_W_OPAQUE
-#define OE_MH_W_OPAQUE 0
-#endif
-template <class T>
-__device__ __forceinline__ T uopaque(T v) {
-  asm volatile("" : "+s"(v));
-  return v;
-}
-
-// The stiff methods' Rosenbrock fallback (dual-number Jacobian, in-register LU) would set
-// the register budget of the whole MH kernel (chain5 'auto': 300 VGPR+AGPR, one wave per
-// SIMD, +49 % per iteration at 262 144 walkers); for S = 5, where the plain DOPRI5 MH
-// kernel runs two waves per SIMD, asking for two keeps the DOPRI5 phase there (80 B of
-// scratch, in the rare path).  S = 6..8 DOPRI5 MH kernels are at one wave per SIMD anyway.
-// The stiff methods' MH with one lane per chain (S <= kStiffRegS) has no iteration-loop kernel:
-// its chains run as rounds of k_mh_tree + k_mh_resolve (below), of one iteration when not
-// speculating.  k_mh's loop around the per-lane DOPRI5 + BDF passes held ~160-380 SGPRs
-// spilled to VGPR lanes (the regime of round 4's unexplained code-shape failures; DESIGN.md
-// §3.6), where the loop-free tree kernel holds ~20; a round costs two launches.
-#ifndef OE_MH_SPREAD  // measurement builds: 0 = MH rounds never spread one lane per wave
-#define OE_MH_SPREAD 1
-#endif
-template <class M, int METHOD>
-constexpr bool kMhRoundsOnly = (METHOD == kAuto || METHOD == kBdf) && M::S <= kStiffRegS;
-
-// INIT: the a-priori fit's pass alone (ma.init, Samplers.py:88-91) — its own kernel, so k_mh's
-// iteration loop is the kernel's only copy of the integrator (with the init branch inside
-// k_mh, the two copies of a stiff method's BDF pass shared one register allocation: ~100 of
-// k_mh<TwoI, auto>'s spilled SGPRs held values across both).
-template <class M, int METHOD, bool INIT = false>
-__global__ void __launch_bounds__(256)
-    __attribute__((amdgpu_waves_per_eu((METHOD == kRosenbrock && M::S == 5) ? 2 : 1)))
-    k_mh(const DevProblem pb, const MHArgs ma) {
-  constexpr int S = M::S;
-  constexpr int PMAX = kPmax<M>;
-#if OE_BDF_CLOCKS
-  if ((threadIdx.x & 63) == 0) bdf_clk_wave_start()[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime();
-#endif
-  const int64_t gw = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = gw < ma.W;
-  const int64_t w = active ? gw : ma.W - 1;
-  const int64_t W0 = ma.W;
-  const int P = pb.P;
-  // The chain state θ [P][W] and y0 [S][W] stays in HBM between iterations (a few loads
-  // per iteration against ~1000 integration steps): only the proposal is held in
-  // registers while integrating, which keeps the DOPRI5 MH kernel within the register
-  // budget of two waves per SIMD.  Tail lanes (w clamped to W-1) never store.
-  double* __restrict__ theta = ma.theta;
-  double* __restrict__ y0g = ma.y0;
-  const uint32_t off = (uint32_t)w * 8u;  // W <= 2^29 (oe_mh_run)
-
-  if constexpr (INIT) {  // a-priori fit (Samplers.py:88-91)
-    const int64_t W = W0;
-    double th[PMAX], y[S];
-#pragma unroll
-    for (int j = 0; j < PMAX; ++j) th[j] = (j < P) ? Row(theta + (int64_t)j * W, W).ld(off) : 0.0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) y[s] = Row(y0g + (int64_t)s * W, W).ld(off);
-    Acc a = acc_init();
-    integrate_walker<M, PMAX, METHOD, false, false, false, kLaneSteps<M, METHOD>>(pb, y, th, nullptr, W, w, active, a);
-    if (active) {
-      const double chi = a.nvalid ? a.chi : __builtin_nan("");
-      Row(ma.cur, W).st(off, chi);
-      Row(ma.cur + W, W).st(off, 1.0 - a.ssres / pb.sstot);
-      Row(ma.cur + 2 * W, W).st(off, -2.0 * (-chi) + 2.0 * (double)pb.pnum);
-      Row(ma.cur + 3 * W, W).st(off, 0.0);
-      if (ma.status) ma.status[w] = finish(a);
-    }
-  } else {
-  // The current chain point (chi, R², AIC, acceptance count; status) also stays in
-  // HBM (cur rows): read after the proposal's integration, written on accept, so none
-  // of it holds registers across the integration.
-  double* __restrict__ cur = ma.cur;
-  const int PS = P + 5;
-
-  for (int it = ma.it0; it < ma.it1; ++it) {
-    // (W re-read per iteration: the row offsets j·W·8 are formed at their use, not hoisted
-    // into the kernel's prologue and kept across the whole loop)
-    int64_t W = OE_MH_W_OPAQUE ? uopaque(W0) : W0;
-    // ---- proposal: θ' = exp(log θ + N(0, sd)) for walking parameters (Framework.py:107-122)
-    double tn[PMAX];
-    theta = opaque(theta);
-    y0g = opaque(y0g);
-    const double* dz = opaque(ma.dz + (int64_t)(it - ma.draw_it0) * P * W);
-    {
-      // one call site each for log and exp: a loop over the parameters, the result put in
-      // place with selects.  Unrolled, every call site is a point where the caller-saved
-      // SGPRs live across the call are spilled to VGPR lanes and restored — 2·PMAX of them.
-      const int Pu = uopaque(P);
-      const uint64_t wm = uopaque(ma.walk_mask);
-#pragma unroll
-      for (int j = 0; j < PMAX; ++j) tn[j] = 0.0;
-#pragma unroll 1
-      for (int j = 0; j < Pu; ++j) {
-        const double thj = Row(theta + (int64_t)j * W, W).ld(off);
-        const double v = ((wm >> j) & 1ull) ? oe_exp(oe_log(thj) + Row(dz + (int64_t)j * W, W).ld(off)) : thj;
-#pragma unroll
-        for (int q = 0; q < PMAX; ++q) tn[q] = (q == j) ? v : tn[q];
-      }
-    }
-    // '<state>0' parameters drive initial states (Samplers.py:110-114)
-    double y[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int pi = uopaque(ma.init_param[s]);
-      y[s] = (uopaque(ma.any_walk) && pi >= 0) ? pick(tn, pi) : Row(y0g + (int64_t)s * W, W).ld(off);
-    }
-    // ---- integrate + fused chi (Samplers.py:115-116)
-    Acc a = acc_init();
-    integrate_walker<M, PMAX, METHOD, false, false, false, kLaneSteps<M, METHOD>>(pb, y, tn, nullptr, W, w, active, a);
-    const double chin = a.nvalid ? a.chi : __builtin_nan("");
-    theta = opaque(theta);
-    y0g = opaque(y0g);
-    cur = opaque(cur);
-    if (OE_MH_W_OPAQUE) W = uopaque(W0);
-#if OE_MH_CHECKS
-    // Integrity of the wave-uniform state every store below depends on:
-    // the row pointers carried through the integration (live in SGPRs or spilled across
-    // ~1000 steps) still equal the kernel arguments, the sample row lies inside the
-    // buffer, linked initial states name a parameter.  Lane offsets are in range by
-    // construction and range-checked by the buffer descriptors.  On a violation nothing
-    // more is stored and the walker's status carries ST_INTERNAL (a recorded assert: a
-    // device trap would take the process — and on this pool possibly the box — down).
-    {
-      bool sound = theta == ma.theta && y0g == ma.y0 && cur == ma.cur &&
-                   (it <= ma.burnin || (it - ma.row0 >= 0 && it - ma.row0 < ma.n_rows));
-#pragma unroll
-      for (int s = 0; s < S; ++s) sound = sound && ma.init_param[s] < P;
-      if (!sound) {
-        if (active && ma.status) ma.status[w] = ST_INTERNAL;
-        return;
-      }
-    }
-#endif
-    const double u = Row(opaque(ma.u + (int64_t)(it - ma.draw_it0) * W), W).ld(off);
-    double chi = Row(cur, W).ld(off), rsq = Row(cur + W, W).ld(off), aic = Row(cur + 2 * W, W).ld(off);
-    double nacc = Row(cur + 3 * W, W).ld(off);
-    // ---- acceptance, in the reference's arithmetic (Samplers.py:124-127)
-    const double lr = oe_exp(chi - chin);
-    const double accp = oe_exp(oe_log(lr));
-    const bool acc = accp > u;
-    const int Pa = uopaque(P);
-    if (acc) {
-      chi = chin;
-      rsq = 1.0 - a.ssres / pb.sstot;
-      aic = -2.0 * (-chi) + 2.0 * (double)pb.pnum;
-      nacc += 1.0;
-      if (active) {
-#pragma unroll
-        for (int j = 0; j < PMAX; ++j)
-          if (j < Pa) Row(theta + (int64_t)j * W, W).st(off, tn[j]);
-        Row(cur, W).st(off, chi);
-        Row(cur + W, W).st(off, rsq);
-        Row(cur + 2 * W, W).st(off, aic);
-        Row(cur + 3 * W, W).st(off, nacc);
-        if (ma.status) ma.status[w] = finish(a);
-      }
-    }
-    // linked initial states follow the current parameters: the accepted proposal, or
-    // on reject the restored ones (Samplers.py:110-114, :137-143)
-    if (uopaque(ma.any_walk) && active) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int pi = uopaque(ma.init_param[s]);
-        if (pi >= 0) Row(y0g + (int64_t)s * W, W).st(off, acc ? pick(tn, pi) : Row(theta + (int64_t)pi * W, W).ld(off));
-      }
-    }
-    // ---- keep the sample after burn-in (Samplers.py:147-153)
-    if (it > ma.burnin && active) {
-      double* row = ma.samples + (int64_t)(it - ma.row0) * PS * W;
-#pragma unroll
-      for (int j = 0; j < PMAX; ++j)
-        if (j < Pa) Row(row + (int64_t)j * W, W).st(off, acc ? tn[j] : Row(theta + (int64_t)j * W, W).ld(off));
-      Row(row + (int64_t)P * W, W).st(off, chi);
-      Row(row + (int64_t)(P + 1) * W, W).st(off, rsq);
-      Row(row + (int64_t)(P + 2) * W, W).st(off, aic);
-      Row(row + (int64_t)(P + 3) * W, W).st(off, (double)it);
-      Row(row + (int64_t)(P + 4) * W, W).st(off, nacc / (double)it);
-    }
-  }
-  }
-}
-
-// ---------------------------------------------------------------------------------
-// Kernel 2b: speculative Metropolis–Hastings for small ensembles (prefetching MH).
-// A chain's proposal at iteration it depends on the chain state, i.e. on which of the
-// earlier proposals were accepted, but its draws (dz[it], u[it]) do not.  One round
-// covers iterations it0 .. it0+d-1: every outcome path of the first j accept/reject
-// decisions gives one candidate state for iteration it0+j, so the 2^d - 1 nodes of the
-// binary tree hold every proposal the chain can make in the round.  k_mh_tree integrates
-// all of them at once (one lane per (node, chain)); k_mh_resolve then walks each chain's
-// tree with the accept test and keeps the path the sequential chain takes.  Each node's
-// proposal is formed by the same operations, in the same order, as k_mh forms it on that
-// path (θ ← exp(log θ + dz) per accepted iteration), and RK4 integrates a lane on its own,
-// so RK4 chains are bitwise those of k_mh; a DOPRI5 lane shares its step size with the 63
-// lanes of its wave, which are other nodes here, so DOPRI5 chains agree within the
-// integration tolerance.  For W chains the round keeps (2^d - 1)·W lanes busy: with few
-// chains the GPU is mostly idle in k_mh, and d iterations cost about one.
-// Node n (heap order): depth j = floor(log2(n + 1)), path bits p = n + 1 - 2^j, bit k of p
-// = the decision at depth k; buffers node-major, [n][W]; 'auto' lanes chain-major (k_mh_tree).
-// ---------------------------------------------------------------------------------
-struct MHTreeArgs {
-  MHArgs m;            // chain state, draws, masks; m.it0 = the round's first iteration
-  int32_t depth;       // iterations of this round (the tree has 2^depth - 1 nodes)
-  int64_t n_lanes;     // (2^depth - 1) * W
-  double* node_th;     // [n][P][W] proposals
-  double* node_chi;    // [n][W] chi of the proposal (NaN if no observation was finite)
-  double* node_ss;     // [n][W] R² residual
-  int32_t* node_st;    // [n][W] status bits
-  int32_t spread;      // 1: one lane per wave (lane 0 of 64-thread workgroups; few lanes, idle device)
-};
-
-template <class M, int METHOD>
-__global__ void __launch_bounds__(256)
-    __attribute__((amdgpu_waves_per_eu((METHOD == kRosenbrock && M::S == 5) ? 2 : 1)))
-    k_mh_tree(const DevProblem pb, const MHTreeArgs ta) {
-  constexpr int S = M::S;
-  constexpr int PMAX = kPmax<M>;
-#if OE_BDF_CLOCKS
-  if ((threadIdx.x & 63) == 0) bdf_clk_wave_start()[threadIdx.x >> 6] = __builtin_amdgcn_s_memtime();
-#endif
-  const MHArgs& ma = ta.m;
-  const int64_t W = ma.W;
-  const int P = pb.P;
-  // spread: each lane alone in its wave (lane 0 of a 64-thread workgroup).  With few lanes
-  // (sequential rounds of a small ensemble) the device is idle anyway, and a wave then costs
-  // its own lane's DOPRI5 + BDF passes instead of its slowest DOPRI5 lane's plus its slowest
-  // BDF lane's, at a uniform wave's pace per step (1.3-1.4x for mixed waves).
-  const int64_t gl = ta.spread ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = gl < ta.n_lanes && (!ta.spread || threadIdx.x == 0);
-  const int64_t gw = active ? gl : ta.n_lanes - 1;
-  // 'auto': chain-major lanes — a wave holds consecutive nodes of one chain, near-identical
-  // proposals that step alike, observe together at little cost and share the BDF pass's
-  // lockstep with proposals of the same stiffness (notebook fit, same box: 0.229 -> 0.221 s,
-  // 1 024 chains 0.706 -> 0.678 s); the other methods keep node-major lanes (a wave = 64 // W
-  // nodes of every chain: synthetic RK4 rounds 7-9 % faster that way, profiles/NOTES.md r04x).
-  // The node buffers are node-major (index g = n·W + c) either way.  n_lanes < 2^29.
-  int64_t n, c;
-  if constexpr (METHOD == kAuto) {
-    const uint32_t nodes = (uint32_t)(ta.n_lanes / W);
-    const uint32_t cq = (uint32_t)gw / nodes;
-    n = (int64_t)((uint32_t)gw - cq * nodes);
-    c = cq;
-  } else {
-    n = gw / W;
-    c = gw - n * W;
-  }
-  const int64_t g = n * W + c;
-  const int j = 31 - __builtin_clz((uint32_t)(n + 1));  // depth
-  const uint32_t path = (uint32_t)(n + 1) - (1u << j);
-  const uint32_t off = (uint32_t)c * 8u;
-  // the chain state this path reaches at depth j: the round's start, moved on by every
-  // accepted proposal of the path, each formed as k_mh forms it
-  double th[PMAX];
-#pragma unroll
-  for (int q = 0; q < PMAX; ++q) th[q] = (q < P) ? Row(ma.theta + (int64_t)q * W, W).ld(off) : 0.0;
-  for (int k = 0; k < j; ++k) {
-    if (!((path >> k) & 1u)) continue;
-    const double* dz = ma.dz + (int64_t)(ma.it0 + k - ma.draw_it0) * P * W;
-#pragma unroll
-    for (int q = 0; q < PMAX; ++q)
-      if (q < P && ((ma.walk_mask >> q) & 1ull)) th[q] = oe_exp(oe_log(th[q]) + Row(dz + (int64_t)q * W, W).ld(off));
-  }
-  double tn[PMAX];
-  {
-    const double* dz = ma.dz + (int64_t)(ma.it0 + j - ma.draw_it0) * P * W;
-#pragma unroll
-    for (int q = 0; q < PMAX; ++q)
-      tn[q] = (q < P && ((ma.walk_mask >> q) & 1ull)) ? oe_exp(oe_log(th[q]) + Row(dz + (int64_t)q * W, W).ld(off))
-                                                      : th[q];
-  }
-  double y[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int pi = ma.init_param[s];
-    y[s] = (ma.any_walk && pi >= 0) ? pick(tn, pi) : Row(ma.y0 + (int64_t)s * W, W).ld(off);
-  }
-  Acc a = acc_init();
-  integrate_walker<M, PMAX, METHOD, false, false, false, kLaneSteps<M, METHOD>>(pb, y, tn, nullptr, ta.n_lanes, g, active, a);
-  if (active) {
-    const int64_t NW = ta.n_lanes;
-    const uint32_t o = (uint32_t)g * 8u;
-#pragma unroll
-    for (int q = 0; q < PMAX; ++q)
-      if (q < P) Row(ta.node_th + n * P * W + (int64_t)q * W, W).st(off, tn[q]);
-    Row(ta.node_chi, NW).st(o, a.nvalid ? a.chi : __builtin_nan(""));
-    Row(ta.node_ss, NW).st(o, a.ssres);
-    ta.node_st[g] = finish(a);
-  }
-}
-
 }  // namespace oe
 #include "stiff_wave.cuh"
 #include "split.cuh"
+#include "mh.cuh"

@@ -25,7 +25,7 @@ namespace oe {
 
 static const char* kBool[2] = {"false", "true"};
 
-// k_mh's iteration loop for method m (ode_kernels.cuh kMhRoundsOnly: the stiff methods of
+// k_mh's iteration loop for method m (mh.cuh kMhRoundsOnly: the stiff methods of
 // register-path models run their chains as k_mh_tree rounds only)
 static bool has_mh_loop(int S, int m) { return !((m == kAuto || m == kBdf) && S <= kStiffRegS); }
 

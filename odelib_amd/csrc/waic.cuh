@@ -4,7 +4,7 @@
 // A trajectory chunk traj [T][S][W] and the context's observation records (Obs, sorted by grid
 // index, read through kconst) give, for record o and walker w,
 //   C = Σ_{s∈mask} y_s (band_columns: from 0.0, increasing state order), d = O − log C,
-//   term = (d·d)/two_s2 (observe()'s operations), valid iff term is finite, e = −term.
+//   term = (d·d)/two_s2 (chi_term, ode_kernels.cuh), valid iff term is finite, e = −term.
 // Per record one cell of five doubles over the valid elements of every chunk folded so far:
 //   n, mean e, M2 e (reduce.cuh's Welford), a = max e, s = Σ exp(e − a):
 //   the online log-sum-exp, so one pass serves any number of chunks.
@@ -98,14 +98,13 @@ __device__ __forceinline__ void waic_accum(const WaicArgs& a) {
   const WalkerRun run = walker_run(a.bpo, a.per_block, a.W);
   const int o = run.row;
   const cptr<Obs> obs = kconst(a.obs);
-  const double O = obs[o].O, two_s2 = obs[o].two_s2;
+  const ObsTerm rec = obs_term(obs + o);
   const double* row = a.traj + (int64_t)obs[o].tidx * a.S * a.W;
   double* trow = a.terms ? a.terms + (int64_t)kconst(a.perm)[o] * a.terms_ld + a.w_offset : nullptr;
   Lse c = lse_empty();
   for_each_walker(row, a.W, obs[o].mask, run, [&](double v, int64_t w) {
     if (w < run.w1) {
-      const double d = O - log(v);
-      const double term = (d * d) / two_s2;
+      const double term = chi_term<true>(rec, v);
       const bool valid = __builtin_isfinite(term);
       if (valid) c.push(-term);
       if (trow) trow[w] = valid ? term : __builtin_nan("");

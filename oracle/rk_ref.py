@@ -100,7 +100,7 @@ def product_split(fp) -> int:
 
 
 def lane_steps(fp) -> bool:
-    """Whether the product's MH kernels step every chain on its own (ode_kernels.cuh
+    """Whether the product's MH kernels step every chain on its own (mh.cuh k_mh, ode_kernels.cuh
     kLaneSteps, lane.cuh, bdf.cuh integrate_bdf_lane): DOPRI5 / 'auto' / 'bdf', one lane per walker, at most
     8 states — step sizes (and BDF orders) per walker, not per lockstep group."""
     return fp.method in ("dopri5", "auto", "bdf") and int(fp.n_states) <= 8 and product_split(fp) == 1
@@ -221,7 +221,7 @@ def philox_draws(seed, gid, it, P, step_sd):
 
 def mh_tree_run(fp, theta, y0, nits, burnin, walk_mask, init_param=None, depth=3, rng="philox", seed=0,
                 replay=None, step_sd=0.05, walker_offset=0, chunk=25, split=None):
-    """The speculative MH rounds of oe_mh_run (oe_mh_args.speculate = depth; ode_kernels.cuh
+    """The speculative MH rounds of oe_mh_run (oe_mh_args.speculate = depth; mh.cuh
     k_mh_tree / capi.hip k_mh_resolve) restated on top of this restatement's batched
     integrate: per round of d iterations the (2^d - 1)·W proposals (node-major lanes n·W + c,
     chain-major c·N + n for 'auto'; node n at depth floor(log2(n+1)), path bits

@@ -434,10 +434,10 @@ __device__ __forceinline__ void integrate_rk4(const DevProblem& pb, double (&y)[
     }
     if (i < pb.T) {  // i == next: an observed grid point
       interval();
-      if constexpr (TRAJ) {
-        store_row_at<S, TRAJ, NT>(trow, y, W, off, active, a);
-        trow += S * W;
-      }
+      // an output time with or without a trajectory: its minimum counts toward ST_NEGATIVE (as
+      // the DOPRI5 kernels' emit() at an observed point, and oracle/rk_ref.c)
+      store_row_at<S, TRAJ, NT>(trow, y, W, off, active, a);
+      if constexpr (TRAJ) trow += S * W;
       observe<S, TRAJ>(pb, i, y, k, a);
       ++i;
     }

@@ -250,6 +250,16 @@ void ref_dopri5_stats(long long* out, int reset) {
     if (reset) g_dp_stats[j] = 0;
   }
 }
+/* End times of the accepted DOPRI5 steps of the group that holds walker 0, in the last call that
+   integrated it (tests/layouts.py puts grid points on them); at most DP_TRACE_MAX are kept */
+#define DP_TRACE_MAX 4096
+static double g_dp_trace[DP_TRACE_MAX];
+static int g_dp_trace_n;
+int ref_dopri5_step_ends(double* out, int cap) {
+  const int n = g_dp_trace_n < cap ? g_dp_trace_n : cap;
+  for (int j = 0; j < n; ++j) out[j] = g_dp_trace[j];
+  return g_dp_trace_n;
+}
 /* Rosenbrock lockstep steps (accepted + rejected) and groups since the last reset (analysis only) */
 void ref_rosenbrock_stats(long long* out, int reset) {
   for (int j = 0; j < 2; ++j) {
@@ -314,6 +324,8 @@ static void dopri5_group(const Prob* pb, Lane* L, int nl, const double* p, doubl
   const double hmin = 1e-14 * fmax(fabs(tend), fabs(t0)) + 1e-300;
   int i = 1, nst = 0, last_rej = 0, nst_all = 0;
   long long n_acc = 0, n_rej = 0;
+  const int trace = L[0].active && L[0].w == 0; /* one group per call: no two writers */
+  if (trace) g_dp_trace_n = 0;
   while (i < pb->T) {
     int last = 0;
     if (t + h >= tend) { h = tend - t; last = 1; }
@@ -417,6 +429,7 @@ static void dopri5_group(const Prob* pb, Lane* L, int nl, const double* p, doubl
         if (!alive) break;
       }
       double tn = last ? tend : t + h;
+      if (trace && g_dp_trace_n < DP_TRACE_MAX) g_dp_trace[g_dp_trace_n++] = tn;
       const double rh = 1.0 / h;
       const double hd1 = h * d1, hd3 = h * d3, hd4 = h * d4, hd5 = h * d5, hd6 = h * d6, hd7 = h * d7;
       while (i < pb->T && pb->times[i] <= tn) {

@@ -161,6 +161,17 @@ def dopri5_stats(reset: bool = True) -> dict:
     return {"accepted": int(out[0]), "rejected": int(out[1]), "groups": int(out[2])}
 
 
+def dopri5_step_ends() -> np.ndarray:
+    """End times of the accepted DOPRI5 steps of the lockstep group that holds walker 0, in the last
+    ``integrate`` that ran it (lane steps: of walker 0 alone)."""
+    L = lib()
+    L.ref_dopri5_step_ends.restype = C.c_int
+    L.ref_dopri5_step_ends.argtypes = [C.c_void_p, C.c_int]
+    out = np.empty(4096)
+    n = L.ref_dopri5_step_ends(out.ctypes.data, len(out))
+    return out[:min(n, len(out))].copy()
+
+
 def rosenbrock_stats(reset: bool = True) -> dict:
     """Rosenbrock lockstep steps (accepted + rejected) and groups since the last reset."""
     out = np.zeros(2, np.int64)

@@ -461,6 +461,66 @@ int oe_waic_accum(oe_ctx* ctx, int64_t n_walkers, const double* traj, double* ac
                   int64_t w_offset, uint32_t flags);
 int oe_waic_finish(oe_ctx* ctx, const double* acc, double* pointwise, double* summary, uint32_t flags);
 
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out over the stored terms --------
+ * (Added under ABI 7: a new struct and a new function, nothing existing changes, OE_ABI_VERSION
+ * stays 7.)  The estimator WAIC's own source recommends over it (Vehtari, Gelman and Gabry 2017;
+ * Vehtari, Simpson, Gelman, Yao and Gabry), with a diagnostic per observation.  It reads the
+ * terms oe_waic_accum stores, where they lie on the device.
+ * For one observation there are N rows whose term t_s = terms[o][s] (s < n_rows) is finite and not
+ * negative; a NaN marks a row that is not valid, as oe_waic_accum writes it, and columns at and
+ * beyond n_rows are not read.  The log-likelihood is ll_s = -t_s + c_o, c_o = log_norm[o].
+ *   Quantities.  r_s = t_s (the log importance ratio up to a constant), a = max r, x_s = r_s - a.
+ *     The tail length is M = ceil(min(N/5, 3 sqrt(N / r_eff))).
+ *   Cutoff.  x_cut = max(the (M+1)-th largest x, log(DBL_MIN)), or -inf if N <= M.  The tail is the
+ *     set of elements with x > x_cut; the comparison is strict, so ties at the cutoff stay in the
+ *     body, and n_tail <= M always.
+ *   No fit.  If n_tail <= 4, pareto_k = +inf and the weights stay raw: lw'_j = x_(j).
+ *   Fit.  Otherwise the tail is sorted ascending, z_j = exp(x_(j)) - exp(x_cut), and (k, sigma)
+ *     are fitted by Zhang and Stephens (2009) as the loo and arviz packages do:
+ *     m = 30 + floor(sqrt(n_tail)); b_j = [1 - sqrt(m/(j - 0.5))] / (3 z_q) + 1/z_max, j = 1..m,
+ *     with z_q = z[int(n_tail/4 + 0.5) - 1] (0-based); k_j = mean log1p(-b_j z);
+ *     L_j = n_tail (log(-b_j/k_j) - k_j - 1); w_j = 1 / sum_l exp(L_l - L_j); weights below
+ *     10 eps are dropped and the rest renormalised; b = sum b_j w_j, k = mean log1p(-b z),
+ *     sigma = -k/b; then pareto_k = (n_tail k + 5)/(n_tail + 10).
+ *     If pareto_k is finite, the j-th smallest tail element (j = 1..n_tail) gets
+ *     lw'_j = min(log(sigma expm1(-pareto_k log1p(-p_j))/pareto_k + exp(x_cut)), 0),
+ *     p_j = (j - 0.5)/n_tail (|pareto_k| < eps: -log1p(-p_j) for the quotient); otherwise the
+ *     weights stay raw.  Body elements keep lw = x.
+ *   Outputs.  den = sum_body exp(x) + sum_tail exp(lw'_j); num = n_body + sum_tail exp(lw'_j - x_(j))
+ *     (a body element's weight times its likelihood is the constant e^(-a));
+ *     elpd_loo_o = log num - a - log den + c_o; lppd_o = log mean exp(ll), as WAIC defines it,
+ *     computed in the same pass from the same terms; p_loo_o = lppd_o - elpd_loo_o.
+ *   pointwise [n_obs][7]: n = N, lppd, elpd_loo, p_loo, pareto_k, n_tail, cutoff (the term at the
+ *     cutoff, the (M+1)-th largest; -inf if N <= M).  N = 0: every field after n is NaN.
+ *   summary [8]: n_obs_used (observations with n >= 1) and over those, added in increasing
+ *     observation order, elpd_loo and p_loo; looic = -2 elpd_loo; se_elpd = sqrt(m var_{m-1}
+ *     (elpd_loo_o)), a two-pass variance (NaN if m < 2); n_k_high, the observations with
+ *     pareto_k > 0.7 (+inf included): there the observation dominates its own estimate; k_max;
+ *     n_rows_min, the smallest n.
+ * The selection is exact: a radix select over the terms' bit patterns, whose counts and maximum
+ * go through integer atomics (order-free).  Every floating-point sum runs in a fixed order
+ * without floating-point atomics, and the tiling depends on (n_obs, n_rows) and the device alone:
+ * every output is the same bits run to run, and, terms being the same bits for any chunking of
+ * the rows, the same bits for any chunking.
+ * Limit: the tail is sorted in LDS, at most 8192 elements, so ceil(min(n_rows/5,
+ * 3 sqrt(n_rows / r_eff))) must not exceed 8192 (r_eff = 1: n_rows <= 7 456 540).
+ * Needs a context, no oe_problem_set.  Launched on the context's stream without a host
+ * synchronisation between the first launch and the last; synchronous on return unless OE_ASYNC.
+ * The context keeps a device scratch of about n_obs (8 KiB + 8 tail bytes) plus the partials.
+ * OE_ERR_STATE without a context.  OE_ERR_ARG: null args, terms, pointwise or summary; n_obs < 1;
+ * n_rows < 1 or above 2^29; terms_ld < n_rows; r_eff not finite and positive; OE_HOST_PTRS; a
+ * tail above the limit. */
+typedef struct {
+  const double* terms;     /* [n_obs][terms_ld] device; NaN = not valid */
+  int32_t n_obs;
+  int64_t n_rows, terms_ld;
+  const double* log_norm;  /* [n_obs] host, c_o; NULL = 0 */
+  double r_eff;            /* > 0; 1.0 = independent draws */
+  double* pointwise;       /* [n_obs][7] device: n, lppd, elpd_loo, p_loo, pareto_k, n_tail, cutoff */
+  double* summary;         /* [8] device: n_obs_used, elpd_loo, p_loo, looic, se_elpd, n_k_high, k_max, n_rows_min */
+} oe_loo_args;
+int oe_loo_run(oe_ctx* ctx, const oe_loo_args* args, uint32_t flags);
+
 /* Device time (ms) of the kernel launches of the last oe_integrate / oe_mh_run,
  * from HIP events recorded on the context's stream around them (waits for them). */
 int oe_last_kernel_ms(oe_ctx* ctx, double* ms);

@@ -178,8 +178,13 @@ def diag_inputs(posterior, pnames):
 COMPARE_COLUMNS = ("elpd_waic", "se_elpd", "p_waic", "waic", "dic", "d_elpd", "se_d")
 
 
-def compare(results):
-    """Rank models by WAIC.  ``results``: a dict mapping a name to what ``ModelFramework.waic``
+LOO_COMPARE_COLUMNS = ("elpd_loo", "se_elpd", "p_loo", "looic", "n_k_high", "d_elpd", "se_d")
+
+
+def compare(results, ic="waic"):
+    """Rank models by WAIC (``ic="loo"``: by PSIS-LOO, with ``ModelFramework.loo``'s results; the
+    table then has the columns elpd_loo, se_elpd, p_loo, looic, n_k_high, d_elpd, se_d and is
+    sorted by ``elpd_loo``).  ``results``: a dict mapping a name to what ``ModelFramework.waic``
     returned for that model (with its ``pointwise`` frame) on one data set.  Returns a DataFrame
     indexed by name, sorted by ``elpd_waic`` with the best (largest) first, with the columns
     elpd_waic, se_elpd, p_waic, waic, dic, d_elpd (the model's elpd_waic minus the best's: 0 for
@@ -205,20 +210,24 @@ def compare(results):
         if not np.array_equal(pw["time"].to_numpy(), first["time"].to_numpy()) or \
                 not np.array_equal(pw["organism"].to_numpy(), first["organism"].to_numpy()):
             raise ValueError(f"{name!r} and {names[0]!r} were scored on different observations")
-    table = pd.DataFrame({c: [results[n].get(c, np.nan) for n in names] for c in COMPARE_COLUMNS[:5]},
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', not {ic!r}")
+    columns = COMPARE_COLUMNS if ic == "waic" else LOO_COMPARE_COLUMNS
+    key = columns[0]
+    table = pd.DataFrame({c: [results[n].get(c, np.nan) for n in names] for c in columns[:5]},
                          index=names, dtype=float)
-    table = table.sort_values("elpd_waic", ascending=False, kind="stable", na_position="last")
+    table = table.sort_values(key, ascending=False, kind="stable", na_position="last")
     best = table.index[0]
     e_best = frames[best]["elpd"].to_numpy(dtype=float)
     d_elpd, se_d = [], []
     for name in table.index:
         d = frames[name]["elpd"].to_numpy(dtype=float) - e_best
         d = d[np.isfinite(d)]
-        d_elpd.append(table.loc[name, "elpd_waic"] - table.loc[best, "elpd_waic"])
+        d_elpd.append(table.loc[name, key] - table.loc[best, key])
         se_d.append(float(np.sqrt(len(d) * np.var(d, ddof=1))) if len(d) > 1 else np.nan)
     table["d_elpd"] = d_elpd
     table["se_d"] = se_d
-    return table[list(COMPARE_COLUMNS)]
+    return table[list(columns)]
 
 
 class ModelFramework:
@@ -657,6 +666,36 @@ class ModelFramework:
             frame, index = self._obs_frame()
             for k in ("n", "lppd", "p_waic", "elpd", "mean_ll", "max_ll"):
                 frame[k] = res[k][index]
+            out["pointwise"] = frame
+        return out
+
+    def loo(self, posteriors, chunk=None, pointwise=True, r_eff=1.0):
+        """PSIS-LOO, the Pareto-smoothed importance-sampling estimate of leave-one-out
+        cross-validation, of this model over every row of ``posteriors`` (as ``waic`` takes
+        them), computed on the device (``Engine.loo``): the ``waic`` pass keeps
+        every row's term per observation, and the importance weights of each observation are
+        smoothed there.  ``r_eff``: the relative efficiency of the draws (``convergence``'s
+        ess / rows; 1.0 takes them as independent) sets the tail length.  Returns a dict:
+        ``elpd_loo`` (larger is better), ``se_elpd``, ``p_loo``, ``looic`` = -2 elpd_loo,
+        ``lppd``, ``n_obs_used``, ``n_k_high`` (observations whose Pareto shape exceeds 0.7, or
+        that had too few tail rows for a fit: each dominates its own estimate, which is then
+        not to be trusted), ``k_max``, ``n_rows_min``, ``n_rows``, ``status_or``, ``n_status``;
+        and, unless ``pointwise=False``, ``pointwise``: one row per observation in ``self.df``
+        order with organism, time, abundance, n, lppd, elpd (the observation's elpd_loo),
+        p_loo, pareto_k, n_tail.  ``compare(results, ic="loo")`` ranks several models' results."""
+        if self.df is None:
+            raise ValueError("loo needs a model with data")
+        theta, y0 = band_inputs(self._pnames, self._snames, self.get_inits(), posteriors)
+        res = self.engine().loo(y0, theta, chunk=chunk, r_eff=r_eff)
+        out = dict(res["summary"])
+        used = res["n"] >= 1
+        out.update(lppd=math.fsum(res["lppd"][used]), n_rows=theta.shape[1], status_or=res["status_or"],
+                   n_status=res["n_status"])
+        if pointwise:
+            frame, index = self._obs_frame()
+            for k, src in (("n", "n"), ("lppd", "lppd"), ("elpd", "elpd_loo"), ("p_loo", "p_loo"),
+                           ("pareto_k", "pareto_k"), ("n_tail", "n_tail")):
+                frame[k] = res[src][index]
             out["pointwise"] = frame
         return out
 

@@ -66,6 +66,7 @@ EXPORTED = (
     "oe_waic_begin",
     "oe_waic_accum",
     "oe_waic_finish",
+    "oe_loo_run",
 )
 
 
@@ -151,6 +152,26 @@ DIAG_FIELDS = ("n_chains", "n", "mean", "W", "B", "var_plus", "rhat", "tau", "es
 WAIC_ACC = 5
 WAIC_POINT_FIELDS = ("n", "lppd", "p_waic", "elpd", "mean_ll", "max_ll")
 WAIC_SUMMARY_FIELDS = ("n_obs_used", "lppd", "p_waic", "elpd_waic", "waic", "se_elpd", "n_high_var", "n_rows_min")
+
+
+class OELooArgs(C.Structure):
+    _fields_ = [
+        ("terms", C.c_void_p),
+        ("n_obs", C.c_int32),
+        ("n_rows", C.c_int64),
+        ("terms_ld", C.c_int64),
+        ("log_norm", C.c_void_p),
+        ("r_eff", C.c_double),
+        ("pointwise", C.c_void_p),
+        ("summary", C.c_void_p),
+    ]
+
+
+# the pointwise columns and summary fields of oe_loo_run, in order
+LOO_POINT_FIELDS = ("n", "lppd", "elpd_loo", "p_loo", "pareto_k", "n_tail", "cutoff")
+LOO_SUMMARY_FIELDS = ("n_obs_used", "elpd_loo", "p_loo", "looic", "se_elpd", "n_k_high", "k_max", "n_rows_min")
+# the largest tail oe_loo_run sorts in LDS: ceil(min(n/5, 3 sqrt(n / r_eff))) must not exceed it
+LOO_TAIL_MAX = 8192
 
 
 _lib = None
@@ -242,6 +263,8 @@ def load_library(path: str | None = None):
         lib.oe_waic_accum.argtypes = [vp, i64, vp, vp, vp, i64, i64, u32]
         lib.oe_waic_finish.restype = C.c_int
         lib.oe_waic_finish.argtypes = [vp, vp, vp, vp, u32]
+        lib.oe_loo_run.restype = C.c_int
+        lib.oe_loo_run.argtypes = [vp, C.POINTER(OELooArgs), u32]
         if lib.oe_abi_version() != OE_ABI_VERSION:
             raise NativeUnavailable("libodelib_amd.so ABI version mismatch; rebuild it")
         if path is None:
@@ -360,6 +383,18 @@ class Context:
     def waic_finish(self, acc, pointwise, summary, flags=0):
         """``oe_waic_finish``: device pointers; ``pointwise`` [n_obs][6], ``summary`` [8]."""
         self._check(self.lib.oe_waic_finish(self._h, acc, pointwise, summary, int(flags)), "oe_waic_finish")
+
+    def loo_run(self, terms, n_obs, n_rows, terms_ld, log_norm, r_eff, pointwise, summary, flags=0):
+        """``oe_loo_run``: ``log_norm`` a host sequence [n_obs] or None, the rest device pointers;
+        ``pointwise`` [n_obs][7], ``summary`` [8]."""
+        import numpy as np
+        c = None if log_norm is None else np.ascontiguousarray(np.asarray(log_norm, dtype=np.float64))
+        if c is not None and len(c) != int(n_obs):
+            raise ValueError("log_norm must have one entry per observation")
+        a = OELooArgs(terms=terms, n_obs=int(n_obs), n_rows=int(n_rows), terms_ld=int(terms_ld),
+                      log_norm=None if c is None else c.ctypes.data, r_eff=float(r_eff), pointwise=pointwise,
+                      summary=summary)
+        self._check(self.lib.oe_loo_run(self._h, C.byref(a), int(flags)), "oe_loo_run")
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)

@@ -4,6 +4,7 @@
 
 #include "band.cuh"
 #include "diag.cuh"
+#include "loo.cuh"
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
 #include "waic.cuh"
@@ -34,3 +35,10 @@ __global__ void __launch_bounds__(256) k_waic_init(double* __restrict__ acc, int
 __global__ void __launch_bounds__(oe::kBandBlock) k_waic_accum(const oe::WaicArgs a);
 __global__ void __launch_bounds__(256) k_waic_merge(const oe::WaicArgs a);
 __global__ void __launch_bounds__(256) k_waic_finish(const oe::WaicArgs a);
+// PSIS-LOO over the stored pointwise terms (loo.cuh): radix select, gather, Pareto fit, summary
+__global__ void __launch_bounds__(oe::kBandBlock) k_loo_select(const oe::LooArgs a);
+__global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_pick(const oe::LooArgs a);
+__global__ void __launch_bounds__(oe::kBandBlock) k_loo_gather(const oe::LooArgs a);
+__global__ void __launch_bounds__(256) k_loo_merge(const oe::LooArgs a);
+__global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_fit(const oe::LooArgs a);
+__global__ void __launch_bounds__(64) k_loo_finish(const oe::LooArgs a);

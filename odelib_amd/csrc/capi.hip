@@ -60,7 +60,9 @@ static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRe
                   plan::kHandBdfWaves == kHandBdfWaves && plan::kResolveLdsDepth == kResolveLdsDepth &&
                   plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile &&
                   plan::kDiagBlock == kDiagBlock && plan::kDiagLB == kDiagLB && plan::kDiagPart == kDiagPart &&
-                  plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc,
+                  plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc && plan::kLooBits == kLooBits &&
+                  plan::kLooPasses == kLooPasses && plan::kLooState == kLooState && plan::kLooAcc == kLooAcc &&
+                  plan::kLooTailMax == kLooTailMax && plan::kLooFitBlock == kLooFitBlock,
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -123,10 +125,12 @@ struct oe_ctx {
   DevBuf diag;       // oe_diag_run's scratch (launch_plan.h DiagPlan)
   DevBuf waic_part;  // k_waic_accum's partials, one cell per workgroup
   DevBuf waic_tab;   // the comparison's tables: c_o [n_obs] doubles (record order), then perm [n_obs] int32
-  std::array<DevBuf*, 12> bufs() {
+  DevBuf loo;        // oe_loo_run's scratch (launch_plan.h LooPlan)
+  std::array<DevBuf*, 13> bufs() {
     return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag, &waic_part,
-            &waic_tab};
+            &waic_tab, &loo};
   }
+  std::vector<double> loo_c;  // oe_loo_run's c_o: the host copy an asynchronous upload reads
   // model comparison (oe_waic_begin .. oe_waic_finish): per observation record (sorted by grid
   // index, as d_obs) the Gaussian normaliser c_o = -(log s_o + log(2 pi)/2) and the caller's
   // index of the record, kept by oe_problem_set
@@ -1327,6 +1331,66 @@ int oe_waic_finish(oe_ctx* c, const double* acc, double* pointwise, double* summ
   a.summary = summary;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_waic_finish), dim3(pl.finish_grid), dim3(pl.finish_block), c->stream, a));
+  return end_timed(c, flags);
+}
+
+// ---- PSIS-LOO over the stored terms (loo.cuh) --------------------------
+int oe_loo_run(oe_ctx* c, const oe_loo_args* g, uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!g) return fail(c, OE_ERR_ARG, "oe_loo_run: args is null");
+  int rc = device_args(c, "oe_loo_run", flags);
+  if (rc) return rc;
+  if (!g->terms || !g->pointwise || !g->summary)
+    return fail(c, OE_ERR_ARG, "oe_loo_run: terms, pointwise and summary are required");
+  if (g->n_obs < 1) return fail(c, OE_ERR_ARG, "oe_loo_run: n_obs must be positive");
+  if (g->n_rows < 1 || g->n_rows > kMaxWalkers) return fail(c, OE_ERR_ARG, "oe_loo_run: n_rows must be in [1, 2^29]");
+  if (g->terms_ld < g->n_rows) return fail(c, OE_ERR_ARG, "oe_loo_run: terms_ld must be at least n_rows");
+  if (!(g->r_eff > 0.0) || !std::isfinite(g->r_eff))
+    return fail(c, OE_ERR_ARG, "oe_loo_run: r_eff must be finite and positive");
+  const plan::LooPlan pl = plan::plan_loo(g->n_obs, g->n_rows, g->r_eff, band_cus(c));
+  if (pl.error)
+    return fail(c, pl.error,
+                "oe_loo_run: the tail of " + std::to_string(g->n_rows) + " rows, " +
+                    std::to_string(plan::loo_tail_len(g->n_rows, g->r_eff)) + " elements, exceeds the limit of " +
+                    std::to_string(plan::kLooTailMax) + " (r_eff = 1: at most 7456540 rows)");
+  OE_DEVICE_GUARD(c);
+  rc = c->loo.reserve(c, pl.bytes);
+  if (rc) return rc;
+  // (an earlier asynchronous call may still read the host copy of c_o)
+  OE_HIP(c, hipStreamSynchronize(c->stream));
+  c->loo_c.assign((size_t)g->n_obs, 0.0);
+  if (g->log_norm) std::copy(g->log_norm, g->log_norm + g->n_obs, c->loo_c.begin());
+  char* base = static_cast<char*>(c->loo.p);
+  LooArgs a{};
+  a.terms = g->terms;
+  a.c = reinterpret_cast<const double*>(base + pl.off_c);
+  a.hist = reinterpret_cast<uint32_t*>(base + pl.off_hist);
+  a.st = reinterpret_cast<unsigned long long*>(base + pl.off_state);
+  a.part = reinterpret_cast<double*>(base + pl.off_part);
+  a.acc = reinterpret_cast<double*>(base + pl.off_acc);
+  a.tail = reinterpret_cast<double*>(base + pl.off_tail);
+  a.pointwise = g->pointwise;
+  a.summary = g->summary;
+  a.r_eff = g->r_eff;
+  a.n_rows = g->n_rows;
+  a.terms_ld = g->terms_ld;
+  a.per_block = pl.per_block;
+  a.n_obs = g->n_obs;
+  a.bpo = pl.blocks_per_obs;
+  a.tail_cap = pl.tail_cap;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, hipMemcpyAsync(base + pl.off_c, c->loo_c.data(), sizeof(double) * (size_t)g->n_obs, hipMemcpyHostToDevice,
+                           c->stream));
+  OE_HIP(c, hipMemsetAsync(base, 0, pl.zero_bytes, c->stream));
+  for (int p = 0; p < kLooPasses; ++p) {
+    a.pass = p;
+    OE_HIP(c, launch(kernel_of(k_loo_select), dim3(pl.grid), dim3(pl.block), c->stream, a));
+    OE_HIP(c, launch(kernel_of(k_loo_pick), dim3(pl.obs_grid), dim3(kLooFitBlock), c->stream, a));
+  }
+  OE_HIP(c, launch(kernel_of(k_loo_gather), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_loo_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_loo_fit), dim3(pl.obs_grid), dim3(kLooFitBlock), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_loo_finish), dim3(1), dim3(64), c->stream, a));
   return end_timed(c, flags);
 }
 

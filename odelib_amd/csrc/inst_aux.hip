@@ -1,6 +1,6 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
 // (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
-// posterior band reductions, the convergence diagnostics, the model-comparison reductions.
+// posterior band reductions, the convergence diagnostics, the model-comparison reductions, PSIS-LOO.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -176,3 +176,11 @@ __global__ void __launch_bounds__(256) k_waic_init(double* __restrict__ acc, int
 __global__ void __launch_bounds__(oe::kBandBlock) k_waic_accum(const oe::WaicArgs a) { oe::waic_accum(a); }
 __global__ void __launch_bounds__(256) k_waic_merge(const oe::WaicArgs a) { oe::waic_merge(a); }
 __global__ void __launch_bounds__(256) k_waic_finish(const oe::WaicArgs a) { oe::waic_finish(a); }
+
+// PSIS-LOO over the stored pointwise terms (loo.cuh)
+__global__ void __launch_bounds__(oe::kBandBlock) k_loo_select(const oe::LooArgs a) { oe::loo_select(a); }
+__global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_pick(const oe::LooArgs a) { oe::loo_pick(a); }
+__global__ void __launch_bounds__(oe::kBandBlock) k_loo_gather(const oe::LooArgs a) { oe::loo_gather(a); }
+__global__ void __launch_bounds__(256) k_loo_merge(const oe::LooArgs a) { oe::loo_merge(a); }
+__global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_fit(const oe::LooArgs a) { oe::loo_fit(a); }
+__global__ void __launch_bounds__(64) k_loo_finish(const oe::LooArgs a) { oe::loo_finish(a); }

@@ -1,11 +1,12 @@
-// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run and the
-// oe_waic_* passes launch, decided by pure functions: numbers in, a plan out (kernel, grids, half
+// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run, the
+// oe_waic_* passes and oe_loo_run launch, decided by pure functions: numbers in, a plan out (kernel, grids, half
 // waves, XCD runs, the hand-over queue's placement, speculation depth, chunk, lag blocks, walker
 // runs, buffer sizes).  No HIP here, so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp,
-// diag_plan_driver.cpp and waic_plan_driver.cpp check the arithmetic on the CPU;
+// diag_plan_driver.cpp, waic_plan_driver.cpp and loo_plan_driver.cpp check the arithmetic on the CPU;
 // capi.hip reserves, fills the arguments and launches.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 
 #include "../../include/odelib_amd.h"
@@ -366,6 +367,76 @@ inline WaicPlan plan_waic(int n_obs, int64_t W, int n_cu) {
   p.grid = b.grid;
   p.partial_bytes = sizeof(double) * kWaicAcc * (size_t)n_obs * (size_t)p.blocks_per_obs;
   p.cell_grid = (unsigned)(((int64_t)n_obs + kBlock - 1) / kBlock);
+  return p;
+}
+
+// ---- oe_loo_run ---------------------------------------------------------------------
+constexpr int kLooBits = 11;          // a digit of the radix select
+constexpr int kLooBins = 1 << kLooBits;
+constexpr int kLooPasses = 6;         // digit passes: 6 x 11 bits cover a term's 64
+constexpr int kLooState = 8;          // 64-bit words of the select's state per observation
+constexpr int kLooAcc = 7;            // doubles per gather cell and per partial
+constexpr int kLooTailMax = 8192;     // doubles of the tail k_loo_fit holds in LDS
+constexpr int kLooFitBlock = 256;
+
+// the tail length M = ceil(min(N/5, 3 sqrt(N / r_eff))) of N valid rows (loo.cuh: the same
+// expression on the device); not decreasing in N
+inline int64_t loo_tail_len(int64_t N, double r_eff) {
+  const double n = (double)N;
+  return (int64_t)std::ceil(std::min(n / 5.0, 3.0 * std::sqrt(n / r_eff)));
+}
+
+struct LooPlan {
+  int error = OE_OK;                      // OE_ERR_ARG: the tail of n_rows valid rows exceeds kLooTailMax
+  unsigned grid = 0, block = kBandBlock;  // k_loo_select / k_loo_gather: grid = n_obs * blocks_per_obs
+  int64_t per_block = 0;                  // consecutive rows of one observation per workgroup
+  int32_t blocks_per_obs = 0;
+  unsigned obs_grid = 0;                  // k_loo_pick / k_loo_fit: one workgroup of kLooFitBlock per observation
+  unsigned cell_grid = 0;                 // k_loo_merge: one lane per observation
+  int32_t tail_cap = 0;                   // doubles per observation of the tail buffer, >= M of any N <= n_rows
+  // the scratch, one buffer: byte offsets of its parts (each a multiple of 256) and the total;
+  // [0, zero_bytes) (the counts and the state) is zeroed before the first pass
+  size_t off_hist = 0;    // [n_obs][kLooBins] uint32
+  size_t off_state = 0;   // [n_obs][kLooState] uint64
+  size_t off_part = 0;    // [n_obs][blocks_per_obs][kLooAcc] doubles
+  size_t off_acc = 0;     // [n_obs][kLooAcc] doubles
+  size_t off_tail = 0;    // [n_obs][tail_cap] doubles
+  size_t off_c = 0;       // [n_obs] doubles: c_o
+  size_t zero_bytes = 0, bytes = 0;
+};
+
+// the most significant bit of pass p's digit
+inline int plan_loo_shift(int pass) { return (kLooPasses - 1 - pass) * kLooBits; }
+
+// 1 <= n_obs, 1 <= n_rows <= 2^29, r_eff finite and positive.  The passes over terms
+// [n_obs][n_rows] are tiled as k_waic_accum's (plan_band_reduce's runs for n_obs rows); the
+// tiling depends on (n_obs, n_rows, n_cu) only.
+inline LooPlan plan_loo(int n_obs, int64_t n_rows, double r_eff, int n_cu) {
+  LooPlan p;
+  const int64_t m_max = loo_tail_len(n_rows, r_eff);
+  if (m_max > kLooTailMax) {
+    p.error = OE_ERR_ARG;
+    return p;
+  }
+  p.tail_cap = (int32_t)std::max<int64_t>(1, m_max);
+  const BandPlan b = plan_band_reduce(n_obs, n_rows, 1, n_cu);
+  p.per_block = b.per_block;
+  p.blocks_per_obs = b.blocks_per_row;
+  p.grid = b.grid;
+  p.obs_grid = (unsigned)n_obs;
+  p.cell_grid = (unsigned)(((int64_t)n_obs + kBlock - 1) / kBlock);
+  auto part = [&p](size_t& off, size_t bytes) {
+    off = p.bytes;
+    p.bytes += (bytes + 255) / 256 * 256;
+  };
+  const size_t rows = (size_t)n_obs;
+  part(p.off_hist, sizeof(uint32_t) * rows * kLooBins);
+  part(p.off_state, sizeof(uint64_t) * rows * kLooState);
+  p.zero_bytes = p.bytes;
+  part(p.off_part, sizeof(double) * rows * (size_t)p.blocks_per_obs * kLooAcc);
+  part(p.off_acc, sizeof(double) * rows * kLooAcc);
+  part(p.off_tail, sizeof(double) * rows * (size_t)p.tail_cap);
+  part(p.off_c, sizeof(double) * rows);
   return p;
 }
 

@@ -176,6 +176,7 @@ def check_resume(resume, rec, numpy_seeds=None, allow_unverified=False):
 
 
 BAND_BUDGET = 1 << 30  # resident trajectory chunk of a band: 1 GiB, as the MH draws' cap
+LOO_TERMS_BUDGET = 4 << 30  # resident terms [n_obs][W] of Engine.loo: 4 GiB
 
 
 def band_chunk(n_times: int, n_states: int, n_walkers: int, budget_bytes: int = BAND_BUDGET) -> int:
@@ -459,6 +460,57 @@ class Engine:
         self._status_result(res, status)
         if terms:
             res["terms"] = terms_t
+        return res
+
+    def loo_terms(self, terms, log_norm=None, r_eff: float = 1.0):
+        """PSIS-LOO of stored pointwise terms (the estimator is stated at
+        ``oe_loo_run`` in include/odelib_amd.h): ``terms`` a device tensor [n_obs][W] as
+        ``waic(..., terms=True)`` returns it (NaN: the row is not valid), read where it lies;
+        ``log_norm`` [n_obs] the normalisers c_o (default 0); ``r_eff`` the relative efficiency
+        of the draws (1.0: independent).  Returns host arrays [n_obs] ``n`` (int64), ``lppd``,
+        ``elpd_loo``, ``p_loo``, ``pareto_k``, ``n_tail`` (int64), ``cutoff``, and the sums as
+        scalars under ``summary`` (``n_obs_used``, ``elpd_loo``, ``p_loo``, ``looic``,
+        ``se_elpd``, ``n_k_high``, ``k_max``, ``n_rows_min``)."""
+        torch = self.torch
+        if not isinstance(terms, torch.Tensor) or terms.dim() != 2:
+            raise ValueError("terms must be a device tensor [n_obs][W]")
+        t = terms.to(device=self.dev, dtype=torch.float64)
+        if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            t = t.contiguous()
+        n_obs, W = int(t.shape[0]), int(t.shape[1])
+        if n_obs < 1 or W < 1:
+            raise ValueError("loo_terms needs at least one observation and one row")
+        point = torch.empty((n_obs, len(N.LOO_POINT_FIELDS)), dtype=torch.float64, device=self.dev)
+        summary = torch.empty(len(N.LOO_SUMMARY_FIELDS), dtype=torch.float64, device=self.dev)
+        self._sync_stream()
+        self.ctx.loo_run(_ptr(t), n_obs, W, int(t.stride(0)), log_norm, r_eff, _ptr(point), _ptr(summary), N.OE_ASYNC)
+        torch.cuda.synchronize(self.dev)
+        pw = point.cpu().numpy()
+        res = {name: pw[:, k].copy() for k, name in enumerate(N.LOO_POINT_FIELDS)}
+        res["n"] = res["n"].astype(np.int64)
+        res["n_tail"] = np.nan_to_num(res["n_tail"], nan=0.0).astype(np.int64)
+        sm = summary.cpu().numpy()
+        res["summary"] = {name: float(sm[k]) for k, name in enumerate(N.LOO_SUMMARY_FIELDS)}
+        return res
+
+    def loo(self, y0, theta, chunk=None, r_eff: float = 1.0, nt_stores: bool = True):
+        """PSIS-LOO of the problem's observations over every walker (posterior row): the
+        ``waic`` pass with ``terms=True``, then ``loo_terms`` on its terms with the problem's
+        c_o = -(log sigma_o + log(2 pi)/2).  Returns ``loo_terms``'s dict, with the WAIC pass's
+        result under ``waic`` and its ``status_or`` and ``n_status``.  The terms stay on the
+        device, n_obs·W·8 bytes: ValueError above ``LOO_TERMS_BUDGET``."""
+        pb = self.problem
+        if pb.n_obs < 1:
+            raise ValueError("loo needs a problem with observations")
+        theta_t = theta if isinstance(theta, self.torch.Tensor) else np.asarray(theta)
+        size = int(pb.n_obs) * int(theta_t.shape[1]) * 8
+        if size > LOO_TERMS_BUDGET:
+            raise ValueError(f"loo keeps the terms of every row on the device: {size} bytes for {pb.n_obs} "
+                             f"observations x {int(theta_t.shape[1])} rows exceed the budget of {LOO_TERMS_BUDGET}")
+        w = self.waic(y0, theta, chunk=chunk, terms=True, nt_stores=nt_stores)
+        sigma = np.asarray(pb.obs_logsigma, dtype=float)
+        res = self.loo_terms(w.pop("terms"), -(np.log(sigma) + 0.5 * np.log(2.0 * np.pi)), r_eff)
+        res.update(waic=w, status_or=w["status_or"], n_status=w["n_status"])
         return res
 
     # -- MCMC convergence diagnostics -------------------------------------------------------------

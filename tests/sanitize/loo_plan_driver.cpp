@@ -1,0 +1,141 @@
+// TEST INFRASTRUCTURE: PSIS-LOO's launch plan (odelib_amd/csrc/launch_plan.h plan_loo) on the
+// CPU, under ASan + UBSan (tests/test_loo_host.py builds and runs it).  Prints the failing case
+// and exits non-zero.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../../include/odelib_amd.h"
+#include "../../odelib_amd/csrc/launch_plan.h"
+
+using namespace oe::plan;
+
+static int g_fail = 0;
+static char g_case[256];
+
+#define CHECK(cond)                                                                \
+  do {                                                                             \
+    if (!(cond)) {                                                                 \
+      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
+      if (++g_fail > 20) std::exit(1);                                             \
+    }                                                                              \
+  } while (0)
+
+int main() {
+  const int64_t Ns[] = {1, 63, 64, 65, 257, 65537, 7400000};
+  const int obs[] = {1, 7, 300};
+  const int ncu[] = {1, 64, 256, 304};
+  for (int n_obs : obs)
+    for (int64_t n_rows : Ns)
+      for (int n_cu : ncu) {
+        std::snprintf(g_case, sizeof g_case, "loo n_obs=%d n_rows=%lld n_cu=%d", n_obs, (long long)n_rows, n_cu);
+        const LooPlan p = plan_loo(n_obs, n_rows, 1.0, n_cu);
+        CHECK(p.error == OE_OK);
+        CHECK(p.block == (unsigned)kBandBlock);
+        CHECK(p.per_block > 0 && p.per_block % kBandTile == 0 && p.blocks_per_obs >= 1);
+        CHECK((int64_t)p.grid == (int64_t)n_obs * p.blocks_per_obs);
+        CHECK(p.obs_grid == (unsigned)n_obs);
+        CHECK((int64_t)p.cell_grid * kBlock >= n_obs && ((int64_t)p.cell_grid - 1) * kBlock < n_obs);
+        // the tiling is k_waic_accum's and depends on (n_obs, n_rows, n_cu) only
+        const WaicPlan w = plan_waic(n_obs, n_rows, n_cu);
+        CHECK(p.per_block == w.per_block && p.blocks_per_obs == w.blocks_per_obs);
+        const LooPlan q = plan_loo(n_obs, n_rows, 0.37, n_cu);
+        CHECK(q.error != OE_OK || (q.per_block == p.per_block && q.blocks_per_obs == p.blocks_per_obs));
+        // the tail capacity holds M of every N the rows can have, and fits the fit kernel's LDS
+        CHECK(p.tail_cap >= 1 && p.tail_cap <= kLooTailMax);
+        CHECK(p.tail_cap >= loo_tail_len(n_rows, 1.0));
+        for (int64_t N : {n_rows, n_rows - 1, n_rows / 2, n_rows / 7, (int64_t)1, (int64_t)0}) {
+          if (N < 0) continue;
+          CHECK(loo_tail_len(N, 1.0) <= p.tail_cap);
+          CHECK(loo_tail_len(N, 1.0) <= std::max<int64_t>(N, 1));
+        }
+        // the scratch: aligned parts in order, none overlapping, the zeroed front holds the counts
+        // and the state
+        const size_t rows = (size_t)n_obs;
+        CHECK(p.off_hist == 0 && p.off_hist % 256 == 0 && p.off_state % 256 == 0 && p.off_part % 256 == 0);
+        CHECK(p.off_acc % 256 == 0 && p.off_tail % 256 == 0 && p.off_c % 256 == 0 && p.bytes % 256 == 0);
+        CHECK(p.off_state >= p.off_hist + sizeof(uint32_t) * rows * kLooBins);
+        CHECK(p.off_part >= p.off_state + sizeof(uint64_t) * rows * kLooState && p.zero_bytes == p.off_part);
+        CHECK(p.off_acc >= p.off_part + sizeof(double) * rows * (size_t)p.blocks_per_obs * kLooAcc);
+        CHECK(p.off_tail >= p.off_acc + sizeof(double) * rows * kLooAcc);
+        CHECK(p.off_c >= p.off_tail + sizeof(double) * rows * (size_t)p.tail_cap);
+        CHECK(p.bytes >= p.off_c + sizeof(double) * rows);
+        // the buffer, indexed as the kernels index it (loo.cuh)
+        std::vector<uint8_t> buf(p.bytes, 0);
+        uint32_t* hist = reinterpret_cast<uint32_t*>(buf.data() + p.off_hist);
+        uint64_t* st = reinterpret_cast<uint64_t*>(buf.data() + p.off_state);
+        double* part = reinterpret_cast<double*>(buf.data() + p.off_part);
+        double* acc = reinterpret_cast<double*>(buf.data() + p.off_acc);
+        double* tail = reinterpret_cast<double*>(buf.data() + p.off_tail);
+        double* c = reinterpret_cast<double*>(buf.data() + p.off_c);
+        std::vector<uint8_t> seen((size_t)n_rows);
+        for (int o = 0; o < n_obs; ++o) {
+          const bool walk = o == 0 || o == n_obs - 1 || o == n_obs / 2;  // the lanes of three observations
+          if (walk) std::fill(seen.begin(), seen.end(), 0);
+          for (unsigned blk = (unsigned)o * p.blocks_per_obs; blk < (unsigned)(o + 1) * p.blocks_per_obs; ++blk) {
+            const int rec = (int)(blk / (unsigned)p.blocks_per_obs), j = (int)(blk - (unsigned)rec * p.blocks_per_obs);
+            CHECK(rec == o && blk < p.grid);
+            const int64_t w0 = (int64_t)j * p.per_block;
+            const int64_t w1 = w0 + p.per_block < n_rows ? w0 + p.per_block : n_rows;
+            CHECK(w0 < n_rows);  // no idle workgroup
+            if (walk)
+              for (int t = 0; t < kBandBlock; ++t)
+                for (int64_t w = w0 + t; w < w1; w += kBandTile)
+                  for (int u = 0; u < kBandTile / kBandBlock; ++u) {
+                    const int64_t wu = w + (int64_t)u * kBandBlock;
+                    if (wu < w1) ++seen.at((size_t)wu);
+                  }
+            for (int k = 0; k < kLooAcc; ++k) part[((int64_t)rec * p.blocks_per_obs + j) * kLooAcc + k] += 1.0;
+          }
+          if (walk) {
+            bool once = true;
+            for (int64_t w = 0; w < n_rows; ++w) once = once && seen[(size_t)w] == 1;
+            CHECK(once);
+          }
+          for (int b = 0; b < kLooBins; ++b) hist[(int64_t)o * kLooBins + b] += 1u;
+          for (int k = 0; k < kLooState; ++k) st[(int64_t)o * kLooState + k] += 1u;
+          for (int k = 0; k < kLooAcc; ++k) acc[(int64_t)o * kLooAcc + k] += 1.0;
+          tail[(int64_t)o * p.tail_cap] += 1.0;
+          tail[(int64_t)o * p.tail_cap + p.tail_cap - 1] += 1.0;
+          c[o] += 1.0;
+        }
+        bool once = true;
+        for (int64_t k = 0; k < (int64_t)n_obs * p.blocks_per_obs * kLooAcc; ++k) once = once && part[k] == 1.0;
+        for (int64_t k = 0; k < (int64_t)n_obs * kLooBins; ++k) once = once && hist[k] == 1u;
+        for (int64_t k = 0; k < (int64_t)n_obs * kLooState; ++k) once = once && st[k] == 1u;
+        for (int64_t k = 0; k < (int64_t)n_obs * kLooAcc; ++k) once = once && acc[k] == 1.0;
+        for (int o = 0; o < n_obs; ++o) once = once && c[o] == 1.0 && tail[(int64_t)o * p.tail_cap] >= 1.0;
+        CHECK(once);
+      }
+  // the digits: six passes of 11 bits from the top cover all 64 bits, each bit once
+  {
+    std::snprintf(g_case, sizeof g_case, "digits");
+    uint64_t covered = 0;
+    for (int pass = 0; pass < kLooPasses; ++pass) {
+      const int s = plan_loo_shift(pass);
+      CHECK(s >= 0 && s < 64);
+      const uint64_t digit = (uint64_t)(kLooBins - 1) << s;  // (bits shifted past 63 are dropped)
+      CHECK((covered & digit) == 0);
+      covered |= digit;
+    }
+    CHECK(covered == ~uint64_t(0));
+    CHECK(plan_loo_shift(kLooPasses - 1) == 0);
+  }
+  // the limit: 3 sqrt(N) <= 8192 up to N = 7 456 540; one row above it is refused
+  {
+    std::snprintf(g_case, sizeof g_case, "limit");
+    CHECK(loo_tail_len(7456540, 1.0) == 8192 && loo_tail_len(7456541, 1.0) == 8193);
+    CHECK(plan_loo(3, 7456540, 1.0, 256).error == OE_OK && plan_loo(3, 7456540, 1.0, 256).tail_cap == 8192);
+    CHECK(plan_loo(3, 7456541, 1.0, 256).error == OE_ERR_ARG);
+    CHECK(plan_loo(3, 40960, 1e-6, 256).error == OE_OK);   // N/5 = 8192 binds
+    CHECK(plan_loo(3, 40961, 1e-6, 256).error == OE_ERR_ARG);
+    // hand-derived: N = 32 000: min(6400, 3 sqrt(32000) = 536.66) -> 537; N = 24: 4.8 -> 5; 25 -> 5; 26 -> 6
+    CHECK(loo_tail_len(32000, 1.0) == 537 && loo_tail_len(24, 1.0) == 5 && loo_tail_len(25, 1.0) == 5);
+    CHECK(loo_tail_len(26, 1.0) == 6 && loo_tail_len(1, 1.0) == 1 && loo_tail_len(0, 1.0) == 0);
+    for (int64_t N = 1; N < 200000; N += 1 + N / 50) CHECK(loo_tail_len(N, 1.0) <= loo_tail_len(N + 1, 1.0));
+  }
+  if (g_fail) return 1;
+  std::printf("SANITIZE OK\n");
+  return 0;
+}

@@ -10,7 +10,7 @@
 // for the median one (oracle/rk_ref.c, tools/lane_steps.py).  Here every step-size decision
 // is the lane's own: HINIT without the wave minimum, the error norm without the wave
 // maximum, the budget eviction of the lane itself; the loop runs until the wave's last lane
-// is done.  The arithmetic of a step is integrate_dopri5's, operation for operation, so a
+// is done.  The arithmetic of a step is integrate_dopri5's (the DOPRI5 step of DESIGN.md §3.0), so a
 // lane's result is the lockstep algorithm on a one-walker group — what the C restatement
 // computes with lane_steps set (oracle/rk_ref.c integrate_group) — and no longer depends on
 // its wave-mates (MH chains are the same whatever chains share their wave, and speculative

@@ -16,7 +16,7 @@
 //   * HINIT's norms (max, exact, any order), the observation sums (passed lane to lane
 //     in state order, so the sum has the one-lane kernel's sequential order) and, at
 //     the end, the status accumulators.
-// Each state's arithmetic is the one-lane kernel's, operation for operation (the split
+// Each state's arithmetic is the one-lane kernel's (the DOPRI5 step of DESIGN.md §3.0; the split
 // RHS below is Chain::rhs element by element); a wave now holds 64/K walkers, which
 // share one step size.  oracle/rk_ref.c restates exactly this (Prob.split = K).
 #pragma once

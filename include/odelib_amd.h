@@ -25,6 +25,10 @@
  *   oe_diag_run      <- nothing in the reference: split R-hat, autocorrelations, effective
  *                       sample size and Monte-Carlo standard error of the kept draws, where
  *                       oe_mh_run left them (the reference offers rawstats' median and sd).
+ *   oe_post_run      <- rawstats (Framework.py:11-17), the reference's whole posterior summary
+ *                       (a log-space mean and sd per column): here count, moments, extremes,
+ *                       histogram and quantiles per selected row, and per pair of rows the
+ *                       covariance cell and a 2-D histogram, of the kept draws where they lie.
  *   oe_allgather_samples <- the pd.concat of the per-process chain posteriors
  *                       (Framework.py:1035-1038) after Pool.starmap (:779-780):
  *                       one RCCL all-gather of the ranks' sample blocks.
@@ -418,6 +422,74 @@ typedef struct {
   double* chain_stats;   /* [n_sel][2][2][W] device, or NULL */
 } oe_diag_args;
 int oe_diag_run(oe_ctx* ctx, const oe_diag_args* args, uint32_t flags);
+
+/* ---- posterior summaries: marginals, quantiles, correlations, pair densities -------------------
+ * (Added under ABI 7: a new struct and a new function, nothing existing changes, so
+ * OE_ABI_VERSION stays 7.)
+ * What are the parameters?  Computed from the kept draws where oe_mh_run left them.
+ *   x = g(samples[k][row][w]) for a selected row, g the identity or the natural log.  An element
+ *   is valid iff x is finite (in a log row a value <= 0 is therefore invalid).
+ *   Marginal, per selected row, pooled over all K W elements of the row, the valid ones:
+ *     n; mean and M2 = sum (x - mean)^2 by Welford pushes (n += 1; d = x - mean; mean += d/n;
+ *     M2 += d (x - mean)) and Chan merges (a then b: n = a.n + b.n, d = b.mean - a.mean,
+ *     rb = b.n/n, mean = a.mean + d rb, M2 = (a.M2 + b.M2) + (d d)(a.n rb); an empty side leaves
+ *     the other side's bits); min and max of x, exact.
+ *     hist: n_bins equal bins on [min, max]; with w = (max - min)/n_bins and t = (x - min)/w the
+ *     bin is n_bins - 1 if t >= n_bins, int(t) if t > 0, else 0; every element in bin 0 when
+ *     max == min.
+ *     Quantile q: r = q (n - 1), k = floor(r).  Rank j lies in the bin b holding ranks
+ *     [c0, c0 + m) and sits at min + w (b + (j - c0 + 1/2)/m); the quantile interpolates the
+ *     positions of ranks k and min(k + 1, n - 1) with weight r - k and is clamped to [min, max].
+ *     It is a value of x: the caller exponentiates for a log row.  n == 0: NaN (and mean, M2,
+ *     min, max are NaN); max == min: that value.
+ *   Pair (i, j) of selected rows, pooled over the elements valid in both rows:
+ *     the cell n, mean_x, mean_y, M2x, M2y, Cxy = sum (x - mean_x)(y - mean_y), by the bivariate
+ *     push n += 1; dx = x - mx; mx += dx/n; dy = y - my; my += dy/n; M2x += dx (x - mx);
+ *     M2y += dy (y - my); Cxy += dx (y - my), and the Chan merge with f = a.n (b.n/n):
+ *     M2x = (a.M2x + b.M2x) + (dx dx) f, M2y likewise, Cxy = (a.Cxy + b.Cxy) + (dx dy) f, dx and
+ *     dy the differences of the sides' means.  n == 0: the other fields are NaN.
+ *     hist2 [n_bins2][n_bins2], x_i major: each axis binned as above on that row's own marginal
+ *     [min, max].
+ *     The caller derives cov = Cxy/(n - 1) and corr = Cxy/sqrt(M2x M2y) (NaN when either M2 is 0).
+ * Outputs (device; the caller zeroes nothing):
+ *   marg  [n_sel][5] doubles: n, mean, M2, min, max;
+ *   hist  [n_sel][n_bins] uint32;
+ *   quant [n_q][n_sel] doubles, NULL iff n_q == 0;
+ *   pair  [n_pairs][6] doubles, NULL iff n_pairs == 0;
+ *   hist2 [n_pairs][n_bins2][n_bins2] uint32, or NULL.
+ * Sums run in a fixed order without floating-point atomics, the counts are integer atomics, and
+ * the tiling of a row depends on K W and the device only: every output is the same bits run to
+ * run, with and without the optional outputs, and a row's marg, hist and quant are the same
+ * bits whatever else is selected.  The cells and the counts are mergeable across ranks (Chan
+ * merges; integer sums once the ranks agree on min and max).
+ * Needs a context, no oe_problem_set.  Launched on the context's stream without a host
+ * synchronisation between the first launch and the last; synchronous on return unless OE_ASYNC.
+ * OE_ERR_ARG: OE_HOST_PTRS, a null samples / marg / hist / rows, K < 1, n_walkers < 1,
+ * K n_walkers >= 2^32 (the counts are uint32), R_tot < 1, n_sel outside 1..16, a row outside
+ * 0..R_tot-1, n_q outside 0..16, quant or q missing when n_q > 0, a probability outside [0, 1],
+ * n_bins outside 16..4096, n_pairs outside 0..120, pair or pairs missing when n_pairs > 0, a
+ * pair index outside 0..n_sel-1 or i == j, n_bins2 outside 4..64 (checked when n_pairs > 0). */
+typedef struct {
+  const double* samples;   /* [K][R_tot][W] device: element (k, row, w) at (k*R_tot + row)*W + w */
+  int32_t K;               /* kept draws per chain */
+  int32_t R_tot;           /* rows per draw (oe_mh_run: P + 5) */
+  int64_t n_walkers;       /* W chains */
+  int32_t n_sel;           /* selected rows, 1..16 */
+  const int32_t* rows;     /* [n_sel] host */
+  const uint8_t* log_rows; /* [n_sel] host: 1 = summarise the natural log of the row; NULL: none */
+  int32_t n_q;             /* quantiles, 0..16 */
+  const double* q;         /* [n_q] host, each in [0, 1] */
+  int32_t n_bins;          /* 16..4096 */
+  int32_t n_pairs;         /* 0..120 */
+  const int32_t* pairs;    /* [n_pairs][2] host: indices i, j into the selected rows, i != j */
+  int32_t n_bins2;         /* 4..64 */
+  double* marg;            /* [n_sel][5] device */
+  uint32_t* hist;          /* [n_sel][n_bins] device */
+  double* quant;           /* [n_q][n_sel] device, NULL iff n_q == 0 */
+  double* pair;            /* [n_pairs][6] device, NULL iff n_pairs == 0 */
+  uint32_t* hist2;         /* [n_pairs][n_bins2][n_bins2] device, or NULL */
+} oe_post_args;
+int oe_post_run(oe_ctx* ctx, const oe_post_args* args, uint32_t flags);
 
 /* ---- posterior-wide model comparison: WAIC and its pointwise terms ----------------------------
  * (Added under ABI 7: three new functions, nothing existing changes, OE_ABI_VERSION stays 7.)

@@ -175,6 +175,49 @@ def diag_inputs(posterior, pnames):
     return np.ascontiguousarray(np.transpose(block, (1, 2, 0)))
 
 
+POST_CHUNK = 65536  # columns of post_inputs' block: the draws are pooled, the shape is only a layout
+
+
+def post_inputs(posterior, pnames):
+    """The posterior DataFrame ``MCMC`` returns -> the [K][P+1][W] array ``Engine.summarize``
+    takes: the ``pnames`` columns and ``chi`` of all N rows, W = min(N, 65 536) per draw slab and
+    K = ceil(N/W) slabs, the tail padded with NaN (not valid, so not counted).  The summaries pool
+    every row: chains of unequal length are fine and the frame's row order is irrelevant.  An
+    empty frame raises ValueError; a missing column raises KeyError."""
+    cols = list(pnames) + ["chi"]
+    block = posterior[cols].to_numpy(dtype=float)
+    n = len(block)
+    if n == 0:
+        raise ValueError("posterior has no rows")
+    W = min(n, POST_CHUNK)
+    K = -(-n // W)
+    full = np.full((K * W, len(cols)), np.nan)
+    full[:n] = block
+    return np.ascontiguousarray(np.transpose(full.reshape(K, W, len(cols)), (0, 2, 1)))
+
+
+def hist_hdi(counts, lo, hi, mass):
+    """The highest-density interval a histogram shows: the shortest run of consecutive bins (the
+    first of several of that length) holding at least ``mass`` of the counts, as the outer edges
+    (left, right) of the run; ``counts`` are equal bins on [lo, hi].  No counts: (nan, nan)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    total = int(c.sum())
+    if total == 0 or len(c) == 0:
+        return float("nan"), float("nan")
+    if not hi > lo:
+        return float(lo), float(hi)
+    need = mass * total
+    cum = np.concatenate([[0], np.cumsum(c)])
+    best, a = None, 0
+    for b in range(1, len(c) + 1):  # bins [a, b): advance a while the run still holds the mass
+        while a + 1 < b and cum[b] - cum[a + 1] >= need:
+            a += 1
+        if cum[b] - cum[a] >= need and (best is None or b - a < best[1] - best[0]):
+            best = (a, b)
+    w = (hi - lo) / len(c)
+    return float(lo + w * best[0]), float(min(lo + w * best[1], hi) if best[1] < len(c) else hi)
+
+
 COMPARE_COLUMNS = ("elpd_waic", "se_elpd", "p_waic", "waic", "dic", "d_elpd", "se_d")
 
 
@@ -601,6 +644,94 @@ class ModelFramework:
                             "stop_lag": res["stop_lag"], "truncated": res["truncated"]},
                            index=pnames + ["chi"])
         return out
+
+    def _post_samples(self, posterior):
+        """what ``posterior_summary`` and ``posterior_pairs`` hand to ``Engine.summarize``"""
+        pnames = self.get_pnames()
+        P = len(pnames)
+        if isinstance(posterior, pd.DataFrame):
+            samples = post_inputs(posterior, pnames)
+        else:
+            samples = posterior["samples"]
+            if samples.dim() != 3 or samples.shape[1] < P + 1:
+                raise ValueError(f"samples must be [K][{P + 5}][W]")
+        return samples, list(range(P + 1)), [1] * P + [0], pnames + ["chi"]
+
+    def posterior_summary(self, posterior, quantiles=(0.025, 0.5, 0.975), hdi=0.95, n_bins=1024):
+        """What are the parameters?  Count, moments, extremes, quantiles and a highest-density
+        interval per parameter and for chi, pooled over every kept draw on the device
+        (``Engine.summarize``).  ``posterior``: the DataFrame ``MCMC`` returns,
+        or the dict ``Samplers.batched_metropolis_hastings(..., return_device=True)`` returns,
+        whose draws are read where they lie.  Parameters are summarised in log space, as
+        ``rawstats`` works; chi as it is.  Returns a DataFrame indexed by ``get_pnames() +
+        ['chi']``: n (valid draws), median and std (``rawstats``' two numbers, from the device's
+        mean and M2 with ddof 1; NaN for chi, which is not logged), mean_log and sd_log (mean and
+        ddof-1 sd of the log; of chi itself for chi), min, max, one ``q<prob>`` column per
+        probability, and hdi_lo, hdi_hi (the shortest run of histogram bins holding ``hdi`` of
+        the draws) -- the last five in the parameter's own units."""
+        samples, rows, logs, names = self._post_samples(posterior)
+        qs = np.asarray(quantiles, dtype=float).reshape(-1)
+        res = self.engine().summarize(samples, rows=rows, log_rows=logs, quantiles=qs, n_bins=n_bins, pairs=None,
+                                      hist=True)
+        lg = np.asarray(logs, dtype=bool)
+        back = lambda v: np.where(lg, np.exp(v), v)  # noqa: E731
+        n, m = res["n"], res["mean"]
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            v = np.where(n > 1, res["m2"] / (n - 1.0), np.nan)
+            out = {"n": n,
+                   "median": np.where(lg, np.exp(m), np.nan),
+                   "std": np.where(lg, ((np.exp(v) - 1) * np.exp(2 * m + v)) ** 0.5, np.nan),
+                   "mean_log": m, "sd_log": np.sqrt(v), "min": back(res["min"]), "max": back(res["max"])}
+            for j, q in enumerate(qs):
+                out[f"q{q:g}"] = back(res["q"][j])
+            ends = np.array([hist_hdi(res["hist"][r], res["min"][r], res["max"][r], hdi) for r in range(len(rows))])
+            out["hdi_lo"], out["hdi_hi"] = back(ends[:, 0]), back(ends[:, 1])
+        return pd.DataFrame(out, index=names)
+
+    def posterior_pairs(self, posterior, n_bins2=32, n_bins=1024, hist=False):
+        """How do the parameters move together?  Correlation and covariance of every pair of
+        parameters (and chi), and the 2-D counts a corner plot draws, pooled over every kept draw
+        on the device (``Engine.summarize``); parameters in log space, chi as it is.  Returns a
+        dict: ``corr`` (unit diagonal), ``cov`` and ``n`` (jointly valid draws) as DataFrames over
+        ``get_pnames() + ['chi']``; ``hist2`` keyed by name pair (a, b), a before b, counts
+        [n_bins2][n_bins2] with a's bins along the first axis; ``edges`` per name, the
+        n_bins2 + 1 bin edges (log space for parameters).  ``hist=True`` adds ``hist`` and
+        ``hist_edges`` per name: the marginal counts of ``n_bins`` bins."""
+        samples, rows, logs, names = self._post_samples(posterior)
+        res = self.engine().summarize(samples, rows=rows, log_rows=logs, quantiles=None, n_bins=n_bins, pairs="all",
+                                      n_bins2=n_bins2, hist=hist, hist2=True)
+        R = len(names)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var = np.where(res["n"] > 1, res["m2"] / (res["n"] - 1.0), np.nan)
+        corr, cov, n = np.eye(R), np.diag(var), np.diag(res["n"])
+        hist2 = {}
+        for p, (i, j) in enumerate(res["pairs"]):
+            corr[i, j] = corr[j, i] = res["corr"][p]
+            cov[i, j] = cov[j, i] = res["cov"][p]
+            n[i, j] = n[j, i] = res["pair_n"][p]
+            hist2[(names[i], names[j])] = res["hist2"][p]
+        frame = lambda a: pd.DataFrame(a, index=names, columns=names)  # noqa: E731
+        out = {"corr": frame(corr), "cov": frame(cov), "n": frame(n), "hist2": hist2,
+               "edges": {nm: np.linspace(res["min"][r], res["max"][r], n_bins2 + 1) for r, nm in enumerate(names)}}
+        if hist:
+            out["hist"] = {nm: res["hist"][r] for r, nm in enumerate(names)}
+            out["hist_edges"] = {nm: np.linspace(res["min"][r], res["max"][r], n_bins + 1) for r, nm in enumerate(names)}
+        return out
+
+    def plot_pairs(self, axes, posterior, n_bins2=32, n_bins=64):
+        """A corner plot on ``axes`` [R][R] (R = parameters + chi): each marginal's counts on the
+        diagonal, the 2-D counts of every pair below it (column name along x, row name along y;
+        log space for parameters), from ``posterior_pairs``, which is returned."""
+        pairs = self.posterior_pairs(posterior, n_bins2=n_bins2, n_bins=n_bins, hist=True)
+        names = list(pairs["corr"].index)
+        if len(axes) != len(names) or any(len(row) != len(names) for row in axes):
+            raise ValueError(f"axes must be [{len(names)}][{len(names)}]")
+        for i, ni in enumerate(names):
+            e = pairs["hist_edges"][ni]
+            axes[i][i].plot(0.5 * (e[:-1] + e[1:]), pairs["hist"][ni], c=str(0.3), lw=1, drawstyle="steps-mid")
+            for j, nj in enumerate(names[:i]):
+                axes[i][j].pcolormesh(pairs["edges"][nj], pairs["edges"][ni], pairs["hist2"][(nj, ni)].T, cmap="Greys")
+        return pairs
 
     def _obs_frame(self):
         """The observations the fit problem holds as rows of ``self.df``, in its order: a frame

@@ -63,6 +63,7 @@ EXPORTED = (
     "oe_band_hist",
     "oe_band_quantiles",
     "oe_diag_run",
+    "oe_post_run",
     "oe_waic_begin",
     "oe_waic_accum",
     "oe_waic_finish",
@@ -146,6 +147,34 @@ class OEDiagArgs(C.Structure):
 
 # the fields of a row of oe_diag_run's summary, in order
 DIAG_FIELDS = ("n_chains", "n", "mean", "W", "B", "var_plus", "rhat", "tau", "ess", "mcse", "stop_lag", "truncated")
+
+
+class OEPostArgs(C.Structure):
+    _fields_ = [
+        ("samples", C.c_void_p),
+        ("K", C.c_int32),
+        ("R_tot", C.c_int32),
+        ("n_walkers", C.c_int64),
+        ("n_sel", C.c_int32),
+        ("rows", C.c_void_p),
+        ("log_rows", C.c_void_p),
+        ("n_q", C.c_int32),
+        ("q", C.c_void_p),
+        ("n_bins", C.c_int32),
+        ("n_pairs", C.c_int32),
+        ("pairs", C.c_void_p),
+        ("n_bins2", C.c_int32),
+        ("marg", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("quant", C.c_void_p),
+        ("pair", C.c_void_p),
+        ("hist2", C.c_void_p),
+    ]
+
+
+# the fields of a row of oe_post_run's marg and of a pair cell, in order
+POST_FIELDS = ("n", "mean", "m2", "min", "max")
+POST_PAIR_FIELDS = ("n", "mean_x", "mean_y", "m2x", "m2y", "cxy")
 
 
 # the cells, pointwise columns and summary fields of the oe_waic_* calls, in order
@@ -257,6 +286,8 @@ def load_library(path: str | None = None):
         lib.oe_band_quantiles.argtypes = [vp, vp, vp, i32, vp, vp, u32]
         lib.oe_diag_run.restype = C.c_int
         lib.oe_diag_run.argtypes = [vp, C.POINTER(OEDiagArgs), u32]
+        lib.oe_post_run.restype = C.c_int
+        lib.oe_post_run.argtypes = [vp, C.POINTER(OEPostArgs), u32]
         lib.oe_waic_begin.restype = C.c_int
         lib.oe_waic_begin.argtypes = [vp, vp]
         lib.oe_waic_accum.restype = C.c_int
@@ -370,6 +401,23 @@ class Context:
                        rows=r.ctypes.data, log_rows=lg.ctypes.data, max_lag=int(max_lag), summary=summary, rho=rho,
                        chain_stats=chain_stats)
         self._check(self.lib.oe_diag_run(self._h, C.byref(a), int(flags)), "oe_diag_run")
+
+    def post_run(self, samples, K, R_tot, n_walkers, rows, log_rows, q, n_bins, pairs, n_bins2, marg, hist,
+                 quant=None, pair=None, hist2=None, flags=0):
+        """``oe_post_run``: ``rows`` / ``log_rows`` / ``q`` / ``pairs`` host sequences, the rest device
+        pointers."""
+        import numpy as np
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        lg = np.ascontiguousarray(np.asarray(log_rows if log_rows is not None else np.zeros(len(r)), dtype=np.uint8))
+        if len(lg) != len(r):
+            raise ValueError("log_rows must have one entry per selected row")
+        qa = np.ascontiguousarray(np.asarray(q if q is not None else [], dtype=np.float64).reshape(-1))
+        pa = np.ascontiguousarray(np.asarray(pairs if pairs is not None else [], dtype=np.int32).reshape(-1, 2))
+        a = OEPostArgs(samples=samples, K=int(K), R_tot=int(R_tot), n_walkers=int(n_walkers), n_sel=len(r),
+                       rows=r.ctypes.data, log_rows=lg.ctypes.data, n_q=len(qa), q=qa.ctypes.data if len(qa) else None,
+                       n_bins=int(n_bins), n_pairs=len(pa), pairs=pa.ctypes.data if len(pa) else None,
+                       n_bins2=int(n_bins2), marg=marg, hist=hist, quant=quant, pair=pair, hist2=hist2)
+        self._check(self.lib.oe_post_run(self._h, C.byref(a), int(flags)), "oe_post_run")
 
     def waic_begin(self, acc):
         """``oe_waic_begin``: ``acc`` a device pointer to [n_obs][5] doubles."""

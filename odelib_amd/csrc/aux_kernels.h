@@ -7,6 +7,7 @@
 #include "loo.cuh"
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
+#include "post.cuh"
 #include "waic.cuh"
 
 // deepest tree k_mh_resolve_wave holds in LDS (4 095 nodes)
@@ -42,3 +43,10 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_loo_gather(const oe::LooArgs
 __global__ void __launch_bounds__(256) k_loo_merge(const oe::LooArgs a);
 __global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_fit(const oe::LooArgs a);
 __global__ void __launch_bounds__(64) k_loo_finish(const oe::LooArgs a);
+// posterior summaries of the kept draws (post.cuh): marginals, quantiles, pair covariances and densities
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_moments(const oe::PostArgs a);
+__global__ void __launch_bounds__(64) k_post_merge(const oe::PostArgs a);
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_hist(const oe::PostArgs a);
+__global__ void __launch_bounds__(256) k_post_quantiles(const oe::PostArgs a);
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_pairs(const oe::PostArgs a);
+__global__ void __launch_bounds__(128) k_post_pair_merge(const oe::PostArgs a);

@@ -62,7 +62,8 @@ static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRe
                   plan::kDiagBlock == kDiagBlock && plan::kDiagLB == kDiagLB && plan::kDiagPart == kDiagPart &&
                   plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc && plan::kLooBits == kLooBits &&
                   plan::kLooPasses == kLooPasses && plan::kLooState == kLooState && plan::kLooAcc == kLooAcc &&
-                  plan::kLooTailMax == kLooTailMax && plan::kLooFitBlock == kLooFitBlock,
+                  plan::kLooTailMax == kLooTailMax && plan::kLooFitBlock == kLooFitBlock &&
+                  plan::kPostMarg == kPostMarg && plan::kPostPair == kPostPair,
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -126,9 +127,10 @@ struct oe_ctx {
   DevBuf waic_part;  // k_waic_accum's partials, one cell per workgroup
   DevBuf waic_tab;   // the comparison's tables: c_o [n_obs] doubles (record order), then perm [n_obs] int32
   DevBuf loo;        // oe_loo_run's scratch (launch_plan.h LooPlan)
-  std::array<DevBuf*, 13> bufs() {
+  DevBuf post;       // oe_post_run's scratch (launch_plan.h PostPlan)
+  std::array<DevBuf*, 14> bufs() {
     return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag, &waic_part,
-            &waic_tab, &loo};
+            &waic_tab, &loo, &post};
   }
   std::vector<double> loo_c;  // oe_loo_run's c_o: the host copy an asynchronous upload reads
   // model comparison (oe_waic_begin .. oe_waic_finish): per observation record (sorted by grid
@@ -1246,6 +1248,104 @@ int oe_diag_run(oe_ctx* c, const oe_diag_args* g, uint32_t flags) {
     a.t0 = plan::plan_diag_first_lag(b);
     OE_HIP(c, launch(kernel_of(k_diag_acov), dim3(pl.grid), dim3(pl.block), c->stream, a));
     OE_HIP(c, launch(kernel_of(k_diag_eval), dim3(pl.row_grid), dim3(kDiagBlock), c->stream, a));
+  }
+  return end_timed(c, flags);
+}
+
+// ---- posterior summaries (post.cuh) -----------------------------------
+namespace {
+
+// workgroups of the streaming passes per CU and row: 2, or OE_POST_WG_PER_CU (measurements)
+int post_wg_per_cu() {
+  static const long n = [] {
+    const char* v = getenv("OE_POST_WG_PER_CU");
+    return v ? strtol(v, nullptr, 10) : 0;
+  }();
+  return n > 0 ? (int)std::min<long>(n, 64) : plan::kPostWgPerCu;
+}
+
+}  // namespace
+
+int oe_post_run(oe_ctx* c, const oe_post_args* g, uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  if (!g) return fail(c, OE_ERR_ARG, "oe_post_run: args is null");
+  const int rc0 = device_args(c, "oe_post_run", flags);
+  if (rc0) return rc0;
+  if (!g->samples || !g->marg || !g->hist || !g->rows)
+    return fail(c, OE_ERR_ARG, "oe_post_run: samples, marg, hist and rows are required");
+  if (g->K < 1) return fail(c, OE_ERR_ARG, "oe_post_run: K must be at least 1");
+  const int64_t W = g->n_walkers;
+  if (W < 1) return fail(c, OE_ERR_ARG, "oe_post_run: n_walkers must be at least 1");
+  if (W >= (int64_t(1) << 32) || (int64_t)g->K * W >= (int64_t(1) << 32))
+    return fail(c, OE_ERR_ARG, "oe_post_run: K * n_walkers must be below 2^32 (the counts are uint32)");
+  if (g->R_tot < 1) return fail(c, OE_ERR_ARG, "oe_post_run: R_tot must be positive");
+  if (g->n_sel < 1 || g->n_sel > kPostMaxRows) return fail(c, OE_ERR_ARG, "oe_post_run: n_sel must be in [1, 16]");
+  for (int r = 0; r < g->n_sel; ++r)
+    if (g->rows[r] < 0 || g->rows[r] >= g->R_tot)
+      return fail(c, OE_ERR_ARG, "oe_post_run: a selected row is outside [0, R_tot)");
+  if (g->n_q < 0 || g->n_q > kPostMaxQ) return fail(c, OE_ERR_ARG, "oe_post_run: n_q must be in [0, 16]");
+  if ((g->n_q > 0) != (g->quant != nullptr) || (g->n_q > 0 && !g->q))
+    return fail(c, OE_ERR_ARG, "oe_post_run: quant and q are required when n_q > 0, and quant is null when n_q == 0");
+  for (int k = 0; k < g->n_q; ++k)
+    if (!(g->q[k] >= 0.0 && g->q[k] <= 1.0)) return fail(c, OE_ERR_ARG, "oe_post_run: q must be in [0, 1]");
+  if (g->n_bins < 16 || g->n_bins > kPostMaxBins) return fail(c, OE_ERR_ARG, "oe_post_run: n_bins must be in [16, 4096]");
+  if (g->n_pairs < 0 || g->n_pairs > kPostMaxPairs) return fail(c, OE_ERR_ARG, "oe_post_run: n_pairs must be in [0, 120]");
+  if ((g->n_pairs > 0) != (g->pair != nullptr) || (g->n_pairs > 0 && !g->pairs))
+    return fail(c, OE_ERR_ARG, "oe_post_run: pair and pairs are required when n_pairs > 0, and pair is null when n_pairs == 0");
+  if (g->n_pairs == 0 && g->hist2) return fail(c, OE_ERR_ARG, "oe_post_run: hist2 needs n_pairs > 0");
+  if (g->n_pairs > 0 && (g->n_bins2 < 4 || g->n_bins2 > kPostMaxBins2))
+    return fail(c, OE_ERR_ARG, "oe_post_run: n_bins2 must be in [4, 64]");
+  for (int p = 0; p < g->n_pairs; ++p) {
+    const int32_t i = g->pairs[2 * p], j = g->pairs[2 * p + 1];
+    if (i < 0 || i >= g->n_sel || j < 0 || j >= g->n_sel || i == j)
+      return fail(c, OE_ERR_ARG, "oe_post_run: a pair's indices must be in [0, n_sel) and differ");
+  }
+  OE_DEVICE_GUARD(c);
+  const plan::PostPlan pl = plan::plan_post((int64_t)g->K * W, g->n_sel, g->n_pairs, c->n_cu, post_wg_per_cu());
+  const int rc = c->post.reserve(c, pl.bytes);
+  if (rc) return rc;
+  char* base = static_cast<char*>(c->post.p);
+  PostArgs a{};
+  a.samples = g->samples;
+  a.marg = g->marg;
+  a.hist = g->hist;
+  a.quant = g->quant;
+  a.pair = g->pair;
+  a.hist2 = g->hist2;
+  a.mpart = reinterpret_cast<double*>(base + pl.off_mpart);
+  a.ppart = reinterpret_cast<double*>(base + pl.off_ppart);
+  a.W = W;
+  a.stride = (int64_t)g->R_tot * W;
+  a.E = (int64_t)g->K * W;
+  a.per_block = pl.per_block;
+  a.n_sel = g->n_sel;
+  a.n_bins = g->n_bins;
+  a.n_q = g->n_q;
+  a.n_pairs = g->n_pairs;
+  a.n_bins2 = g->n_pairs > 0 ? g->n_bins2 : 0;
+  a.bpr = pl.blocks_per_row;
+  for (int r = 0; r < g->n_sel; ++r) {
+    a.rows[r] = g->rows[r];
+    if (g->log_rows && g->log_rows[r]) a.log_mask |= 1u << r;
+  }
+  for (int k = 0; k < g->n_q; ++k) a.q[k] = g->q[k];
+  for (int p = 0; p < g->n_pairs; ++p) {
+    a.pair_i[p] = (uint8_t)g->pairs[2 * p];
+    a.pair_j[p] = (uint8_t)g->pairs[2 * p + 1];
+  }
+  // the host lists travel in the kernels' arguments: nothing of the caller's is read after return
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, hipMemsetAsync(g->hist, 0, sizeof(uint32_t) * (size_t)g->n_sel * (size_t)g->n_bins, c->stream));
+  OE_HIP(c, launch(kernel_of(k_post_moments), dim3(pl.row_grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_post_merge), dim3(1), dim3(64), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_post_hist), dim3(pl.row_grid), dim3(pl.block), c->stream, a));
+  if (g->n_q > 0) OE_HIP(c, launch(kernel_of(k_post_quantiles), dim3(1), dim3(256), c->stream, a));
+  if (g->n_pairs > 0) {
+    if (g->hist2)
+      OE_HIP(c, hipMemsetAsync(g->hist2, 0, sizeof(uint32_t) * (size_t)g->n_pairs * (size_t)g->n_bins2 * (size_t)g->n_bins2,
+                               c->stream));
+    OE_HIP(c, launch(kernel_of(k_post_pairs), dim3(pl.pair_grid), dim3(pl.block), c->stream, a));
+    OE_HIP(c, launch(kernel_of(k_post_pair_merge), dim3(1), dim3(128), c->stream, a));
   }
   return end_timed(c, flags);
 }

@@ -1,6 +1,7 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
 // (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
-// posterior band reductions, the convergence diagnostics, the model-comparison reductions, PSIS-LOO.
+// posterior band reductions, the convergence diagnostics, the model-comparison reductions, PSIS-LOO,
+// the posterior summaries.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -184,3 +185,11 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_loo_gather(const oe::LooArgs
 __global__ void __launch_bounds__(256) k_loo_merge(const oe::LooArgs a) { oe::loo_merge(a); }
 __global__ void __launch_bounds__(oe::kLooFitBlock) k_loo_fit(const oe::LooArgs a) { oe::loo_fit(a); }
 __global__ void __launch_bounds__(64) k_loo_finish(const oe::LooArgs a) { oe::loo_finish(a); }
+
+// posterior summaries of the kept draws (post.cuh)
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_moments(const oe::PostArgs a) { oe::post_moments(a); }
+__global__ void __launch_bounds__(64) k_post_merge(const oe::PostArgs a) { oe::post_merge(a); }
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_hist(const oe::PostArgs a) { oe::post_hist(a); }
+__global__ void __launch_bounds__(256) k_post_quantiles(const oe::PostArgs a) { oe::post_quantiles(a); }
+__global__ void __launch_bounds__(oe::kBandBlock) k_post_pairs(const oe::PostArgs a) { oe::post_pairs(a); }
+__global__ void __launch_bounds__(128) k_post_pair_merge(const oe::PostArgs a) { oe::post_pair_merge(a); }

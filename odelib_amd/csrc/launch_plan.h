@@ -1,8 +1,8 @@
-// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run, the
+// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run, oe_post_run, the
 // oe_waic_* passes and oe_loo_run launch, decided by pure functions: numbers in, a plan out (kernel, grids, half
 // waves, XCD runs, the hand-over queue's placement, speculation depth, chunk, lag blocks, walker
 // runs, buffer sizes).  No HIP here, so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp,
-// diag_plan_driver.cpp, waic_plan_driver.cpp and loo_plan_driver.cpp check the arithmetic on the CPU;
+// diag_plan_driver.cpp, post_plan_driver.cpp, waic_plan_driver.cpp and loo_plan_driver.cpp check the arithmetic on the CPU;
 // capi.hip reserves, fills the arguments and launches.
 #pragma once
 #include <algorithm>
@@ -486,6 +486,47 @@ inline DiagPlan plan_diag(int32_t K, int64_t W, int32_t n_sel, int32_t max_lag) 
   part(p.off_acov, sizeof(double) * rows * (size_t)(p.max_lag + 1));
   part(p.off_state, sizeof(double) * rows * kDiagState);
   part(p.off_done, sizeof(int32_t) * rows);
+  return p;
+}
+
+// ---- oe_post_run --------------------------------------------------------------------
+constexpr int kPostMarg = 5;         // doubles per row of marg and per moments partial
+constexpr int kPostPair = 6;         // doubles per pair cell and per pair partial
+constexpr int kPostWgPerCu = 2;      // workgroups per CU and row (or pair): the best of 2, 4, 8, 16 measured
+
+struct PostPlan {
+  unsigned block = kBandBlock;
+  unsigned row_grid = 0;    // k_post_moments / k_post_hist: n_sel * blocks_per_row
+  unsigned pair_grid = 0;   // k_post_pairs: n_pairs * blocks_per_row
+  int64_t per_block = 0;    // consecutive elements e = k*W + w of one row per workgroup, <= 2^30
+  int32_t blocks_per_row = 0;
+  // the scratch, one buffer: byte offsets of its parts (each a multiple of 256) and the total
+  size_t off_mpart = 0;     // [n_sel][blocks_per_row][kPostMarg] doubles
+  size_t off_ppart = 0;     // [n_pairs][blocks_per_row][kPostPair] doubles
+  size_t bytes = 0;
+};
+
+// 1 <= n_elem = K*W < 2^32 elements per row, 1 <= n_sel <= 16 rows, 0 <= n_pairs <= 120 pairs.
+// Workgroup (r, j) folds elements [j * per_block, min(n_elem, (j + 1) * per_block)) of row (or
+// pair) r; runs are a multiple of kBandTile.  The runs depend on (n_elem, n_cu, wg_per_cu) only,
+// not on what else is selected: a row's bits do not depend on its company.
+inline PostPlan plan_post(int64_t n_elem, int32_t n_sel, int32_t n_pairs, int n_cu, int wg_per_cu = kPostWgPerCu) {
+  PostPlan p;
+  const int64_t tiles = (n_elem + kBandTile - 1) / kBandTile;
+  const int64_t want = std::max<int64_t>(4, (int64_t)wg_per_cu * n_cu);  // (at least 4: a run fits 2^30)
+  const int64_t bpr0 = std::min(tiles, want);
+  const int64_t tiles_per_block = (tiles + bpr0 - 1) / bpr0;
+  p.per_block = tiles_per_block * kBandTile;
+  p.blocks_per_row = (int32_t)((tiles + tiles_per_block - 1) / tiles_per_block);
+  p.row_grid = (unsigned)((int64_t)n_sel * p.blocks_per_row);
+  p.pair_grid = (unsigned)((int64_t)n_pairs * p.blocks_per_row);
+  auto part = [&p](size_t& off, size_t bytes) {
+    off = p.bytes;
+    p.bytes += (bytes + 255) / 256 * 256;
+  };
+  const size_t bpr = (size_t)p.blocks_per_row;
+  part(p.off_mpart, sizeof(double) * (size_t)n_sel * bpr * kPostMarg);
+  part(p.off_ppart, sizeof(double) * (size_t)n_pairs * bpr * kPostPair);
   return p;
 }
 

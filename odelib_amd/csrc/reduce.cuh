@@ -1,5 +1,5 @@
-// reduce.cuh — the fixed-order reduction across walkers that band.cuh, diag.cuh and waic.cuh
-// share.
+// reduce.cuh — the fixed-order reduction across walkers that band.cuh, diag.cuh, waic.cuh and
+// post.cuh share.
 //
 // Determinism: every floating-point merge runs in one fixed order — a lane's own elements in
 // walker order, the wave's 64 lanes (wave_fold: six DPP hops, lane 63 read), the workgroup's
@@ -45,6 +45,47 @@ __device__ __forceinline__ Welford merge(const Welford& a, const Welford& b) {
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ Welford shifted(const Welford& a) {
   return Welford{dpp_f64<CTRL, ROW_MASK>(a.n), dpp_f64<CTRL, ROW_MASK>(a.mean), dpp_f64<CTRL, ROW_MASK>(a.m2)};
+}
+
+// count, means, M2x = Σ(x − mx)², M2y and Cxy = Σ(x − mx)(y − my) of the pairs pushed so far
+struct Cov {
+  double n, mx, my, m2x, m2y, cxy;
+  __device__ __forceinline__ void push(double x, double y) {
+    n += 1.0;
+    const double dx = x - mx;
+    mx += dx / n;
+    const double dy = y - my;
+    my += dy / n;
+    m2x += dx * (x - mx);
+    m2y += dy * (y - my);
+    cxy += dx * (y - my);
+  }
+};
+
+// Chan: a then b, the M2 parts as Welford's (an empty side leaves the other's bits as they are)
+__device__ __forceinline__ Cov merge(const Cov& a, const Cov& b) {
+  Cov r;
+  r.n = a.n + b.n;
+  const double dx = b.mx - a.mx, dy = b.my - a.my;
+  const double rb = b.n / r.n;
+  const double f = a.n * rb;
+  const double mx = a.mx + dx * rb, my = a.my + dy * rb;
+  const double m2x = (a.m2x + b.m2x) + (dx * dx) * f;
+  const double m2y = (a.m2y + b.m2y) + (dy * dy) * f;
+  const double cxy = (a.cxy + b.cxy) + (dx * dy) * f;
+  const bool ae = a.n == 0.0, be = b.n == 0.0;
+  r.mx = be ? a.mx : ae ? b.mx : mx;
+  r.my = be ? a.my : ae ? b.my : my;
+  r.m2x = be ? a.m2x : ae ? b.m2x : m2x;
+  r.m2y = be ? a.m2y : ae ? b.m2y : m2y;
+  r.cxy = be ? a.cxy : ae ? b.cxy : cxy;
+  return r;
+}
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ Cov shifted(const Cov& a) {
+  return Cov{dpp_f64<CTRL, ROW_MASK>(a.n),   dpp_f64<CTRL, ROW_MASK>(a.mx),  dpp_f64<CTRL, ROW_MASK>(a.my),
+             dpp_f64<CTRL, ROW_MASK>(a.m2x), dpp_f64<CTRL, ROW_MASK>(a.m2y), dpp_f64<CTRL, ROW_MASK>(a.cxy)};
 }
 
 // a plain sum

@@ -556,6 +556,70 @@ class Engine:
             res["chain_stats"] = cs_t.cpu().numpy()
         return res
 
+    # -- posterior summaries -----------------------------------------------------------------------
+    def summarize(self, samples, rows=None, log_rows=None, quantiles=(0.025, 0.5, 0.975), n_bins=1024, pairs="all",
+                  n_bins2=32, hist=False, hist2=False):
+        """Marginal moments, extremes and quantiles of kept draws, and the covariance of pairs of
+        rows (the estimator is stated at ``oe_post_run`` in include/odelib_amd.h).
+
+        ``samples``: a device tensor or host array [K][R_tot][W] (``mh_run``'s ``samples``: a
+        device tensor is read where it lies).  ``rows``: the rows to summarise (default: all, at
+        most 16); ``log_rows``: per selected row, whether its natural log is summarised (default:
+        none).  ``pairs``: "all" (every i < j of the selected rows), a list of index pairs into the
+        selected rows, or None.  Everything returned is in the row's transformed space (the log of
+        a log row).  Returns a dict of host arrays: ``n``, ``mean``, ``m2``, ``min``, ``max``
+        [n_sel]; ``q`` [n_q][n_sel]; ``pairs`` [n_pairs][2]; ``pair_n``, ``mean_x``, ``mean_y``,
+        ``m2x``, ``m2y``, ``cxy``, ``cov``, ``corr`` [n_pairs]; ``hist`` [n_sel][n_bins] and
+        ``hist2`` [n_pairs][n_bins2][n_bins2] (first row of the pair major) when asked."""
+        torch = self.torch
+        if isinstance(samples, torch.Tensor):
+            s = samples.to(device=self.dev, dtype=torch.float64).contiguous()
+        else:
+            s = torch.as_tensor(np.ascontiguousarray(np.asarray(samples, dtype=np.float64)), device=self.dev)
+        if s.dim() != 3:
+            raise ValueError("samples must be [K][R_tot][W]")
+        K, R_tot, W = (int(v) for v in s.shape)
+        sel = np.arange(R_tot, dtype=np.int32) if rows is None else np.asarray(rows, dtype=np.int32).reshape(-1)
+        lg = np.zeros(len(sel), dtype=np.uint8) if log_rows is None else np.asarray(log_rows).astype(np.uint8).reshape(-1)
+        if len(lg) != len(sel):
+            raise ValueError("log_rows must have one entry per selected row")
+        qa = np.asarray(() if quantiles is None else quantiles, dtype=np.float64).reshape(-1)
+        if isinstance(pairs, str):
+            if pairs != "all":
+                raise ValueError('pairs must be "all", a list of index pairs or None')
+            pa = np.array([(i, j) for i in range(len(sel)) for j in range(i + 1, len(sel))], dtype=np.int32).reshape(-1, 2)
+        else:
+            pa = np.asarray([] if pairs is None else pairs, dtype=np.int32).reshape(-1, 2)
+        n_sel, n_q, n_pairs = len(sel), len(qa), len(pa)
+        u32 = torch.int32  # the counts are uint32: viewed as such on the host
+        marg = torch.empty((n_sel, len(N.POST_FIELDS)), dtype=torch.float64, device=self.dev)
+        hist_t = torch.empty((n_sel, max(int(n_bins), 1)), dtype=u32, device=self.dev)
+        quant = torch.empty((n_q, n_sel), dtype=torch.float64, device=self.dev) if n_q else None
+        pair = torch.empty((n_pairs, len(N.POST_PAIR_FIELDS)), dtype=torch.float64, device=self.dev) if n_pairs else None
+        hist2_t = (torch.empty((n_pairs, int(n_bins2), int(n_bins2)), dtype=u32, device=self.dev)
+                   if hist2 and n_pairs and n_bins2 > 0 else None)
+        self._sync_stream()
+        self.ctx.post_run(_ptr(s), K, R_tot, W, sel, lg, qa, n_bins, pa, n_bins2, _ptr(marg), _ptr(hist_t), _ptr(quant),
+                          _ptr(pair), _ptr(hist2_t), N.OE_ASYNC)
+        torch.cuda.synchronize(self.dev)
+        m = marg.cpu().numpy()
+        res = {name: m[:, k].copy() for k, name in enumerate(N.POST_FIELDS)}
+        res["q"] = quant.cpu().numpy() if n_q else np.empty((0, n_sel))
+        res["pairs"] = pa
+        pc = pair.cpu().numpy() if n_pairs else np.empty((0, len(N.POST_PAIR_FIELDS)))
+        for k, name in enumerate(N.POST_PAIR_FIELDS):
+            res["pair_n" if name == "n" else name] = pc[:, k].copy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            res["cov"] = np.where(res["pair_n"] > 1, res["cxy"] / (res["pair_n"] - 1.0), np.nan)
+            den = res["m2x"] * res["m2y"]
+            res["corr"] = np.where(den > 0, res["cxy"] / np.sqrt(den), np.nan)
+        if hist:
+            res["hist"] = hist_t.cpu().numpy().view(np.uint32)
+        if hist2:
+            res["hist2"] = (hist2_t.cpu().numpy().view(np.uint32) if hist2_t is not None
+                            else np.empty((0, int(n_bins2), int(n_bins2)), dtype=np.uint32))
+        return res
+
     def last_kernel_ms(self) -> float:
         return self.ctx.last_kernel_ms()
 

@@ -593,6 +593,67 @@ typedef struct {
 } oe_loo_args;
 int oe_loo_run(oe_ctx* ctx, const oe_loo_args* args, uint32_t flags);
 
+/* ---- Sobol' sensitivity indices: first-order and total effects over a Saltelli design ----------
+ * (Added under ABI 7: a new struct and three new functions, nothing existing changes,
+ * OE_ABI_VERSION stays 7.)  Which factor moves which output, and when?  Variance-based global
+ * sensitivity (Sobol' 1993; Saltelli et al. 2010; Jansen 1999), per row (a grid time) and column.
+ * Design.  N base rows, d factors, two independent sample matrices A and B; AB_i is A with
+ *   factor i taken from B.  G = d + 2 groups of N walkers: group 0 = A, group 1 = B, group
+ *   2 + i = AB_i.  The caller builds the groups and produces their outputs (oe_integrate);
+ *   these calls only reduce them.
+ * Chunk.  values [n_rows][n_states][G nb] doubles, the layout oe_integrate writes: nb base rows,
+ *   group-major, walker g nb + n.  The base rows are split into n_blocks replicate blocks;
+ *   every chunk belongs to one block.
+ * Output.  C = sum of the states in col_mask[c], added in increasing state order from 0.0.
+ *   log_form != 0: f = log C, valid iff C is finite and > 0;  log_form == 0: f = C, valid iff C
+ *   is finite.
+ * Cells, per (block, row, column), OE_SOBOL_CELL(d) = 3 + 6 d doubles over the block's base rows n:
+ *   the variance cell n_V, mean, M2: f_A(n) then f_B(n) of every base row valid in A and B
+ *     (Welford per lane, Chan merges);
+ *   per factor i the cell n_i, mx, my, M2x, M2y, Cxy of the pairs (x = f_B(n), y = f_ABi(n) - f_A(n))
+ *     over the base rows valid in A, B and AB_i, by the bivariate push and Chan merge stated at
+ *     oe_post_run (the two means share one reciprocal 1/n per push).
+ *   acc [n_blocks][n_rows][n_cols][3 + 6 d]; validity is per factor, and n_V and n_i say what
+ *   was dropped.
+ * oe_sobol_finish merges the blocks' cells in block order and writes
+ *   idx [n_rows][n_cols][d][3]: S1_i = (Cxy / n_i) / V  (Saltelli 2010, centred),
+ *       ST_i = ((M2y / n_i + my^2) / 2) / V  (Jansen: E[(f_A - f_ABi)^2] / 2V), n_i;
+ *   out [n_rows][n_cols][3]: n_V, mean, V = M2 / n_V.
+ *   V == 0 (every valid value alike), n_V == 0 or n_i == 0: S1_i = ST_i = NaN.  An AB_i group that
+ *   is a bitwise copy of A gives S1_i == ST_i == 0.0 exactly.
+ *   acc is left as it is (more chunks may follow); the caller derives standard errors from the
+ *   per-block cells, which hold the same fields.
+ * Merges run in a fixed order (lane, wave, workgroup, the workgroups' partials in block order,
+ * the replicate blocks in block order) without floating-point atomics: every output is the same
+ * bits run to run for one chunking; the counts are the same for any chunking, the rest agrees
+ * across chunkings to rounding.  The cells are mergeable across ranks (Chan merges).
+ * Order of calls: oe_sobol_begin (empties acc); oe_sobol_accum for every chunk; oe_sobol_finish.
+ * The shapes come from the struct, not from oe_problem_set: needs a context only, and the same
+ * calls fold any per-walker scalar (chi [W] as n_rows = n_states = n_cols = 1, mask 1).
+ * Device pointers only (col_mask is a host array, read during the call); launched on the
+ * context's stream; synchronous on return unless OE_ASYNC.
+ * OE_ERR_STATE without a context.  OE_ERR_ARG: null args, col_mask, acc, values, idx or out;
+ * OE_HOST_PTRS; n_rows outside 1..2^24; n_states outside 1..64; n_cols outside 1..64; n_factors
+ * outside 1..32; n_base < 1 or (n_factors + 2) n_base > 2^29; n_blocks outside 1..min(1024,
+ * n_base); a mask that is zero or selects a state >= n_states; an accumulator above 2^31 doubles;
+ * block outside 0..n_blocks-1; nb outside 1..n_base. */
+#define OE_SOBOL_CELL(n_factors) (3 + 6 * (n_factors))
+typedef struct {
+  int32_t n_rows;           /* rows of a chunk (grid times) */
+  int32_t n_states;         /* states per row, 1..64 */
+  int32_t n_cols;           /* output columns, 1..64 */
+  const uint64_t* col_mask; /* [n_cols] host: the states a column sums */
+  int32_t n_factors;        /* d, 1..32 */
+  int64_t n_base;           /* N, base rows of the whole design */
+  int32_t log_form;         /* non-zero: f = log C */
+  int32_t n_blocks;         /* replicate blocks of base rows */
+} oe_sobol_args;
+int oe_sobol_begin(oe_ctx* ctx, const oe_sobol_args* args, double* acc, uint32_t flags);
+int oe_sobol_accum(oe_ctx* ctx, const oe_sobol_args* args, int32_t block, int64_t nb, const double* values,
+                   double* acc, uint32_t flags);
+int oe_sobol_finish(oe_ctx* ctx, const oe_sobol_args* args, const double* acc, double* idx, double* out,
+                    uint32_t flags);
+
 /* Device time (ms) of the kernel launches of the last oe_integrate / oe_mh_run,
  * from HIP events recorded on the context's stream around them (waits for them). */
 int oe_last_kernel_ms(oe_ctx* ctx, double* ms);

@@ -830,6 +830,100 @@ class ModelFramework:
             out["pointwise"] = frame
         return out
 
+    # ------------------------------------------------------------------ global sensitivity
+    def _sobol_factors(self, parameters, ranges):
+        """name -> an object with ``dist``, ``hp`` and ``val`` for every factor: the parameters
+        named (default: every parameter with a prior or a range), each with its range or,
+        failing that, its prior."""
+        ranges = dict(ranges or {})
+        for p in ranges:
+            if p not in self.parameters:
+                raise ValueError(f"unknown parameter {p!r} in ranges; this model's are {', '.join(self._pnames)}")
+        names = [p for p in self._pnames if p in ranges or self.parameters[p].has_distribution()] \
+            if parameters is None else list(parameters)
+        drawn = {}
+        for p in names:
+            if p not in self.parameters:
+                raise ValueError(f"unknown parameter {p!r}; this model's are {', '.join(self._pnames)}")
+            par = self.parameters[p]
+            if p in ranges:
+                r = ranges[p]
+                if not hasattr(r, "ppf"):
+                    lo, hi = (float(v) for v in r)
+                    if not hi > lo:
+                        raise ValueError(f"range of {p!r}: ({lo}, {hi}) is empty")
+                    from scipy.stats import uniform
+                    r = uniform(loc=lo, scale=hi - lo)
+                drawn[p] = parameter(stats_gen=r, hyperparameters={}, init_value=par.val, name=p)
+            elif par.has_distribution():
+                drawn[p] = par
+            else:
+                raise ValueError(f"parameter {p!r} has no prior: give it a range to make it a factor")
+        if not drawn:
+            raise ValueError("sobol needs at least one factor: a parameter with a prior or a range")
+        return drawn
+
+    def sobol(self, n_base=4096, parameters=None, ranges=None, seed=0, log=True, blocks=8, chunk=None):
+        """Which parameter moves which state, and when?  First-order (``S1``) and total
+        (``ST``) Sobol' indices of every output column per grid time, and of chi, over a
+        Saltelli design drawn through the priors (``Samplers.sample_saltelli``) and integrated
+        and reduced on the device (``Engine.sobol``): ``n_base`` (d + 2)
+        integrations for d factors.
+
+        ``parameters``: the factors (default: every parameter with a prior or a range); the
+        others keep their value.  ``ranges``: name -> a scipy frozen distribution or (lo, hi),
+        which overrides or supplies a prior.  A '<state>0' parameter moves that state's initial
+        value with it.  ``log``: the indices are those of the log of a column (rows that are
+        not finite and positive are left out; ``n`` counts the rest) or of the column itself.
+        ``blocks``: replicate blocks for the standard errors.  Returns two DataFrames: a long
+        one, one row per output column, parameter and grid time (time, organism, parameter, S1,
+        ST, S1_se, ST_se, n), and one row per parameter for chi (parameter, S1, ST, S1_se,
+        ST_se, n).  Both carry ``status_or`` and ``n_status`` in ``attrs``, and ``n_valid``, ``mean``
+        and ``var`` of the output itself ([T][columns] arrays for the long frame, scalars for chi).  Where every row
+        gives the same value (the initial time, unless an initial value is a factor) the
+        variance is zero and the indices are NaN."""
+        drawn = self._sobol_factors(parameters, ranges)
+        fa, fb = Samplers.sample_saltelli(drawn, n_base, seed)
+        for frame in (fa, fb):
+            for p in self._pnames:
+                if p not in drawn:
+                    frame[p] = float(np.asarray(self.parameters[p].val))
+        theta_a, y0_a = band_inputs(self._pnames, self._snames, self.get_inits(), fa)
+        theta_b, y0_b = band_inputs(self._pnames, self._snames, self.get_inits(), fb)
+        factors = [([self._pnames.index(p)], [self._snames.index(p[:-1])] if p.endswith('0') and p[:-1] in self._snames
+                    else []) for p in drawn]
+        res = self.engine().sobol(theta_a, theta_b, y0_a, y0_b, factors, log=log, col_masks=self._band_masks(),
+                                  blocks=blocks, chunk=chunk)
+        names, fnames = self.get_snames(after_summation=True), list(drawn)
+        T, C, d = len(self.times), len(names), len(fnames)
+        out = {"time": np.tile(self.times, C * d), "organism": np.repeat(names, d * T),
+               "parameter": np.tile(np.repeat(fnames, T), C)}
+        for k in ("S1", "ST", "S1_se", "ST_se", "n"):
+            out[k] = np.transpose(res[k], (1, 2, 0)).reshape(-1)  # [T][C][d] -> column, factor, time
+        long = pd.DataFrame(out)
+        chi = pd.DataFrame({"parameter": fnames, **{k: res["chi"][k] for k in ("S1", "ST", "S1_se", "ST_se", "n")}})
+        for k in ("n_valid", "mean", "var"):  # of the pooled values of A and B: [T][columns], and chi's scalars
+            long.attrs[k] = res[k]
+            chi.attrs[k] = res["chi"][k].item()
+        for frame in (long, chi):
+            frame.attrs["status_or"], frame.attrs["n_status"] = res["status_or"], res["n_status"]
+        return long, chi
+
+    def plot_sobol(self, ax, result, variable, which="ST"):
+        """One line per parameter over time: the ``which`` index ("ST" or "S1") of ``variable``
+        from ``sobol``'s result (its long frame, or the pair it returns)."""
+        frame = result[0] if isinstance(result, tuple) else result
+        if which not in ("S1", "ST"):
+            raise ValueError('which must be "S1" or "ST"')
+        b = frame[frame["organism"] == variable]
+        if b.empty:
+            raise ValueError(f"unknown variable {variable!r}; the columns are {', '.join(self.get_snames())}")
+        for name, g in b.groupby("parameter", sort=False):
+            ax.plot(g["time"], g[which], lw=1, label=name)
+        ax.set_ylabel(which)
+        ax.legend()
+        return ax
+
     # ------------------------------------------------------------------ LHS survey
     def _lhs_samples(self, samples=100, **kwargs):
         """LHS draws through the priors; parameters without a prior (and not remapped in

@@ -31,6 +31,29 @@ def lhs_classic(n, samples):
     return H
 
 
+def _through_priors(parameter_dict, unit):
+    """``sample_lhs``'s mapping for given points: unit-cube points [samples][dims] through each
+    prior's ppf, one dimension per non-zero element of a parameter's value: a DataFrame with one column per name (an
+    array-valued parameter yields one array per sample; its zero elements stay zero)."""
+    width = {name: int(np.count_nonzero(par.val)) for name, par in parameter_dict.items()}
+    columns, first = {}, 0
+    for name, par in parameter_dict.items():
+        block = par.dist.ppf(unit[:, first:first + width[name]], **par.hp)
+        first += width[name]
+        if width[name] == 1:
+            columns[name] = block.ravel()
+            continue
+        template = np.array(par.val, dtype=float)
+        slots = template != 0
+        rows = []
+        for draw in block:
+            row = template.copy()
+            row[slots] = draw
+            rows.append(row)
+        columns[name] = rows
+    return pd.DataFrame(columns)
+
+
 def sample_lhs(parameter_dict, samples):
     """Latin-hypercube samples of the parameters in ``parameter_dict`` (name -> parameter
     with a prior), mapped through each prior's ppf (Samplers.py:6-51).  An array-valued
@@ -54,6 +77,28 @@ def sample_lhs(parameter_dict, samples):
             rows.append(row)
         columns[name] = rows
     return pd.DataFrame(columns)
+
+
+def sample_saltelli(parameter_dict, n_base, seed=0):
+    """The two independent sample matrices A and B of a Saltelli design for Sobol' indices:
+    ``n_base`` points of ONE scrambled Sobol' sequence in 2k dimensions (k the dimensions
+    ``sample_lhs`` would use), the first k giving A and the last k giving B, each mapped
+    through the prior's ppf exactly as ``sample_lhs`` maps its hypercube.  Every entry of
+    ``parameter_dict`` is a factor and needs a prior (``dist`` / ``hp``); ``n_base`` must be a
+    power of two (the sequence's balance properties hold only there).  Returns the DataFrames
+    (A, B), one column per name; the same seed gives the same bits."""
+    n_base = int(n_base)
+    if n_base < 1 or n_base & (n_base - 1):
+        raise ValueError(f"n_base must be a power of two, got {n_base}")
+    for name, par in parameter_dict.items():
+        if not par.dist:
+            raise ValueError(f"parameter {name!r} has no prior: it cannot be a factor")
+    from scipy.stats import qmc
+    k = sum(int(np.count_nonzero(par.val)) for par in parameter_dict.values())
+    if k < 1:
+        raise ValueError("sample_saltelli needs at least one factor")
+    unit = qmc.Sobol(2 * k, scramble=True, seed=seed).random(n_base)
+    return _through_priors(parameter_dict, unit[:, :k]), _through_priors(parameter_dict, unit[:, k:])
 
 
 def _posterior_frame(samples, pnames, static_parameters, chains, kept):

@@ -68,6 +68,9 @@ EXPORTED = (
     "oe_waic_accum",
     "oe_waic_finish",
     "oe_loo_run",
+    "oe_sobol_begin",
+    "oe_sobol_accum",
+    "oe_sobol_finish",
 )
 
 
@@ -203,6 +206,30 @@ LOO_SUMMARY_FIELDS = ("n_obs_used", "elpd_loo", "p_loo", "looic", "se_elpd", "n_
 LOO_TAIL_MAX = 8192
 
 
+class OESobolArgs(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_int32),
+        ("n_states", C.c_int32),
+        ("n_cols", C.c_int32),
+        ("col_mask", C.c_void_p),
+        ("n_factors", C.c_int32),
+        ("n_base", C.c_int64),
+        ("log_form", C.c_int32),
+        ("n_blocks", C.c_int32),
+    ]
+
+
+# the fields oe_sobol_finish writes per (row, column, factor) and per (row, column), in order
+SOBOL_IDX_FIELDS = ("S1", "ST", "n")
+SOBOL_OUT_FIELDS = ("n_valid", "mean", "var")
+
+
+def sobol_cell(n_factors: int) -> int:
+    """OE_SOBOL_CELL: doubles per accumulator cell of the oe_sobol_* calls (the variance cell n,
+    mean, M2, then per factor n, mx, my, M2x, M2y, Cxy)."""
+    return 3 + 6 * int(n_factors)
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -296,6 +323,12 @@ def load_library(path: str | None = None):
         lib.oe_waic_finish.argtypes = [vp, vp, vp, vp, u32]
         lib.oe_loo_run.restype = C.c_int
         lib.oe_loo_run.argtypes = [vp, C.POINTER(OELooArgs), u32]
+        lib.oe_sobol_begin.restype = C.c_int
+        lib.oe_sobol_begin.argtypes = [vp, C.POINTER(OESobolArgs), vp, u32]
+        lib.oe_sobol_accum.restype = C.c_int
+        lib.oe_sobol_accum.argtypes = [vp, C.POINTER(OESobolArgs), i32, i64, vp, vp, u32]
+        lib.oe_sobol_finish.restype = C.c_int
+        lib.oe_sobol_finish.argtypes = [vp, C.POINTER(OESobolArgs), vp, vp, vp, u32]
         if lib.oe_abi_version() != OE_ABI_VERSION:
             raise NativeUnavailable("libodelib_amd.so ABI version mismatch; rebuild it")
         if path is None:
@@ -443,6 +476,32 @@ class Context:
                       log_norm=None if c is None else c.ctypes.data, r_eff=float(r_eff), pointwise=pointwise,
                       summary=summary)
         self._check(self.lib.oe_loo_run(self._h, C.byref(a), int(flags)), "oe_loo_run")
+
+    @staticmethod
+    def sobol_args(n_rows, n_states, col_masks, n_factors, n_base, log_form, n_blocks):
+        """An ``oe_sobol_args`` for the three ``oe_sobol_*`` calls; ``col_masks`` a host sequence
+        (kept alive by the returned struct)."""
+        import numpy as np
+        m = np.ascontiguousarray(np.asarray(col_masks, dtype=np.uint64).reshape(-1))
+        a = OESobolArgs(n_rows=int(n_rows), n_states=int(n_states), n_cols=len(m), col_mask=m.ctypes.data,
+                        n_factors=int(n_factors), n_base=int(n_base), log_form=1 if log_form else 0,
+                        n_blocks=int(n_blocks))
+        a._masks = m
+        return a
+
+    def sobol_begin(self, args, acc, flags=0):
+        """``oe_sobol_begin``: ``acc`` a device pointer to [n_blocks][n_rows][n_cols][sobol_cell(d)] doubles."""
+        self._check(self.lib.oe_sobol_begin(self._h, C.byref(args), acc, int(flags)), "oe_sobol_begin")
+
+    def sobol_accum(self, args, block, nb, values, acc, flags=0):
+        """``oe_sobol_accum``: ``values`` [n_rows][n_states][(d + 2) nb] on the device, folded into
+        the cells of replicate block ``block``."""
+        self._check(self.lib.oe_sobol_accum(self._h, C.byref(args), int(block), int(nb), values, acc, int(flags)),
+                    "oe_sobol_accum")
+
+    def sobol_finish(self, args, acc, idx, out, flags=0):
+        """``oe_sobol_finish``: device pointers; ``idx`` [n_rows][n_cols][d][3], ``out`` [n_rows][n_cols][3]."""
+        self._check(self.lib.oe_sobol_finish(self._h, C.byref(args), acc, idx, out, int(flags)), "oe_sobol_finish")
 
     def last_kernel_ms(self) -> float:
         ms = C.c_double(0.0)

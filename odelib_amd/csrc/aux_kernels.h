@@ -8,6 +8,7 @@
 #include "numpy_rng.cuh"
 #include "ode_kernels.cuh"
 #include "post.cuh"
+#include "sobol.cuh"
 #include "waic.cuh"
 
 // deepest tree k_mh_resolve_wave holds in LDS (4 095 nodes)
@@ -50,3 +51,8 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_post_hist(const oe::PostArgs
 __global__ void __launch_bounds__(256) k_post_quantiles(const oe::PostArgs a);
 __global__ void __launch_bounds__(oe::kBandBlock) k_post_pairs(const oe::PostArgs a);
 __global__ void __launch_bounds__(128) k_post_pair_merge(const oe::PostArgs a);
+// Sobol' sensitivity indices (sobol.cuh): the Saltelli design's groups reduced across base rows
+__global__ void __launch_bounds__(256) k_sobol_init(double* __restrict__ acc, int64_t n_doubles);
+__global__ void __launch_bounds__(oe::kBandBlock) k_sobol_accum(const oe::SobolArgs a);
+__global__ void __launch_bounds__(256) k_sobol_merge(const oe::SobolArgs a);
+__global__ void __launch_bounds__(256) k_sobol_finish(const oe::SobolArgs a);

@@ -63,7 +63,8 @@ static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRe
                   plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc && plan::kLooBits == kLooBits &&
                   plan::kLooPasses == kLooPasses && plan::kLooState == kLooState && plan::kLooAcc == kLooAcc &&
                   plan::kLooTailMax == kLooTailMax && plan::kLooFitBlock == kLooFitBlock &&
-                  plan::kPostMarg == kPostMarg && plan::kPostPair == kPostPair,
+                  plan::kPostMarg == kPostMarg && plan::kPostPair == kPostPair &&
+                  plan::kSobolVar == kSobolVar && plan::kSobolCov == kSobolCov && OE_SOBOL_CELL(7) == sobol_cell(7),
               "launch_plan.h and the kernels disagree");
 
 // what the plans need to know of a model: which slots its Entry fills
@@ -128,9 +129,10 @@ struct oe_ctx {
   DevBuf waic_tab;   // the comparison's tables: c_o [n_obs] doubles (record order), then perm [n_obs] int32
   DevBuf loo;        // oe_loo_run's scratch (launch_plan.h LooPlan)
   DevBuf post;       // oe_post_run's scratch (launch_plan.h PostPlan)
-  std::array<DevBuf*, 14> bufs() {
+  DevBuf sobol_part; // k_sobol_accum's partials, one cell per workgroup and column
+  std::array<DevBuf*, 15> bufs() {
     return {&scratch, &draws, &np_state, &stiff, &tree, &obs, &hq, &band_part, &band_tab, &diag, &waic_part,
-            &waic_tab, &loo, &post};
+            &waic_tab, &loo, &post, &sobol_part};
   }
   std::vector<double> loo_c;  // oe_loo_run's c_o: the host copy an asynchronous upload reads
   // model comparison (oe_waic_begin .. oe_waic_finish): per observation record (sorted by grid
@@ -1491,6 +1493,110 @@ int oe_loo_run(oe_ctx* c, const oe_loo_args* g, uint32_t flags) {
   OE_HIP(c, launch(kernel_of(k_loo_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
   OE_HIP(c, launch(kernel_of(k_loo_fit), dim3(pl.obs_grid), dim3(kLooFitBlock), c->stream, a));
   OE_HIP(c, launch(kernel_of(k_loo_finish), dim3(1), dim3(64), c->stream, a));
+  return end_timed(c, flags);
+}
+
+// ---- Sobol' sensitivity indices (sobol.cuh) -----------------------------
+namespace {
+
+// workgroups of k_sobol_accum per CU: launch_plan.h's, or OE_SOBOL_WG_PER_CU (measurements)
+int sobol_wg_per_cu() {
+  static const long n = [] {
+    const char* v = getenv("OE_SOBOL_WG_PER_CU");
+    return v ? strtol(v, nullptr, 10) : 0;
+  }();
+  return n > 0 ? (int)std::min<long>(n, 64) : plan::kSobolWgPerCu;
+}
+
+// the shapes of a design, checked; OE_OK with the kernels' arguments filled but for the pointers
+int sobol_args(oe_ctx* c, const char* who, const oe_sobol_args* g, uint32_t flags, SobolArgs* a) {
+  const std::string w = who;
+  if (!g) return fail(c, OE_ERR_ARG, w + ": args is null");
+  if (flags & OE_HOST_PTRS) return fail(c, OE_ERR_ARG, w + ": device pointers only");
+  if (g->n_rows < 1 || g->n_rows > (1 << 24)) return fail(c, OE_ERR_ARG, w + ": n_rows must be in [1, 2^24]");
+  if (g->n_states < 1 || g->n_states > 64) return fail(c, OE_ERR_ARG, w + ": n_states must be in [1, 64]");
+  if (g->n_cols < 1 || g->n_cols > kSobolMaxCols) return fail(c, OE_ERR_ARG, w + ": n_cols must be in [1, 64]");
+  if (!g->col_mask) return fail(c, OE_ERR_ARG, w + ": col_mask is required");
+  if (g->n_factors < 1 || g->n_factors > kSobolMaxFactors)
+    return fail(c, OE_ERR_ARG, w + ": n_factors must be in [1, 32]");
+  if (g->n_base < 1 || (int64_t)(g->n_factors + 2) * g->n_base > kMaxWalkers)
+    return fail(c, OE_ERR_ARG, w + ": n_base must be at least 1 and (n_factors + 2) * n_base at most 2^29");
+  if (g->n_blocks < 1 || g->n_blocks > kSobolMaxBlocks || g->n_blocks > g->n_base)
+    return fail(c, OE_ERR_ARG, w + ": n_blocks must be in [1, min(1024, n_base)]");
+  const uint64_t all = g->n_states == 64 ? ~0ull : (1ull << g->n_states) - 1;
+  for (int k = 0; k < g->n_cols; ++k)
+    if (!g->col_mask[k] || (g->col_mask[k] & ~all))
+      return fail(c, OE_ERR_ARG, w + ": a column mask (col_mask) selects no / unknown states");
+  const double doubles = (double)g->n_blocks * g->n_rows * g->n_cols * sobol_cell(g->n_factors);
+  if (doubles > 2147483648.0)
+    return fail(c, OE_ERR_ARG, w + ": n_blocks * n_rows * n_cols cells exceed 2^31 doubles");
+  *a = SobolArgs{};
+  a->n_rows = g->n_rows;
+  a->n_states = g->n_states;
+  a->n_cols = g->n_cols;
+  a->d = g->n_factors;
+  a->n_blocks = g->n_blocks;
+  a->log_form = g->log_form ? 1 : 0;
+  for (int k = 0; k < g->n_cols; ++k) a->masks[k] = g->col_mask[k];
+  return OE_OK;
+}
+
+}  // namespace
+
+int oe_sobol_begin(oe_ctx* c, const oe_sobol_args* g, double* acc, uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  SobolArgs a;
+  const int rc = sobol_args(c, "oe_sobol_begin", g, flags, &a);
+  if (rc) return rc;
+  if (!acc) return fail(c, OE_ERR_ARG, "oe_sobol_begin: acc is required");
+  OE_DEVICE_GUARD(c);
+  const plan::SobolPlan pl = plan::plan_sobol(a.n_rows, 1, a.n_cols, a.d, a.n_blocks, c->n_cu);
+  const int64_t doubles = (int64_t)(pl.cell_bytes / sizeof(double)) * a.n_blocks;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_sobol_init), dim3(pl.init_grid), dim3(kBlock), c->stream, acc, doubles));
+  return end_timed(c, flags);
+}
+
+int oe_sobol_accum(oe_ctx* c, const oe_sobol_args* g, int32_t block, int64_t nb, const double* values, double* acc,
+                   uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  SobolArgs a;
+  int rc = sobol_args(c, "oe_sobol_accum", g, flags, &a);
+  if (rc) return rc;
+  if (!values || !acc) return fail(c, OE_ERR_ARG, "oe_sobol_accum: values and acc are required");
+  if (block < 0 || block >= a.n_blocks) return fail(c, OE_ERR_ARG, "oe_sobol_accum: block must be in [0, n_blocks)");
+  if (nb < 1 || nb > g->n_base) return fail(c, OE_ERR_ARG, "oe_sobol_accum: nb must be in [1, n_base]");
+  OE_DEVICE_GUARD(c);
+  const plan::SobolPlan pl = plan::plan_sobol(a.n_rows, nb, a.n_cols, a.d, a.n_blocks, c->n_cu, sobol_wg_per_cu());
+  rc = c->sobol_part.reserve(c, pl.partial_bytes);
+  if (rc) return rc;
+  a.values = values;
+  a.acc = acc;
+  a.part = static_cast<double*>(c->sobol_part.p);
+  a.nb = nb;
+  a.per_block = pl.per_block;
+  a.bpr = pl.blocks_per_row;
+  a.block = block;
+  // the masks travel in the kernels' arguments: nothing of the caller's is read after return
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_sobol_accum), dim3(pl.grid), dim3(pl.block), c->stream, a));
+  OE_HIP(c, launch(kernel_of(k_sobol_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
+  return end_timed(c, flags);
+}
+
+int oe_sobol_finish(oe_ctx* c, const oe_sobol_args* g, const double* acc, double* idx, double* out, uint32_t flags) {
+  if (!c || !c->own_stream) return OE_ERR_STATE;
+  SobolArgs a;
+  const int rc = sobol_args(c, "oe_sobol_finish", g, flags, &a);
+  if (rc) return rc;
+  if (!acc || !idx || !out) return fail(c, OE_ERR_ARG, "oe_sobol_finish: acc, idx and out are required");
+  OE_DEVICE_GUARD(c);
+  const plan::SobolPlan pl = plan::plan_sobol(a.n_rows, 1, a.n_cols, a.d, a.n_blocks, c->n_cu);
+  a.acc = const_cast<double*>(acc);
+  a.idx = idx;
+  a.out = out;
+  OE_HIP(c, hipEventRecord(c->ev0, c->stream));
+  OE_HIP(c, launch(kernel_of(k_sobol_finish), dim3(pl.finish_grid), dim3(kBlock), c->stream, a));
   return end_timed(c, flags);
 }
 

@@ -1,7 +1,7 @@
 // inst_aux.hip — the model-independent kernels the C-ABI launches beside a model's own
 // (aux_kernels.h): the stiff walker list, the proposal draws, the MH rounds' resolution, the
 // posterior band reductions, the convergence diagnostics, the model-comparison reductions, PSIS-LOO,
-// the posterior summaries.
+// the posterior summaries, the Sobol' sensitivity indices.
 // Device code only, built and linked with the model units (inst_*.hip).
 #include "aux_kernels.h"
 
@@ -193,3 +193,11 @@ __global__ void __launch_bounds__(oe::kBandBlock) k_post_hist(const oe::PostArgs
 __global__ void __launch_bounds__(256) k_post_quantiles(const oe::PostArgs a) { oe::post_quantiles(a); }
 __global__ void __launch_bounds__(oe::kBandBlock) k_post_pairs(const oe::PostArgs a) { oe::post_pairs(a); }
 __global__ void __launch_bounds__(128) k_post_pair_merge(const oe::PostArgs a) { oe::post_pair_merge(a); }
+
+// Sobol' sensitivity indices over a Saltelli design (sobol.cuh)
+__global__ void __launch_bounds__(256) k_sobol_init(double* __restrict__ acc, int64_t n_doubles) {
+  oe::sobol_init(acc, n_doubles);
+}
+__global__ void __launch_bounds__(oe::kBandBlock) k_sobol_accum(const oe::SobolArgs a) { oe::sobol_accum(a); }
+__global__ void __launch_bounds__(256) k_sobol_merge(const oe::SobolArgs a) { oe::sobol_merge(a); }
+__global__ void __launch_bounds__(256) k_sobol_finish(const oe::SobolArgs a) { oe::sobol_finish(a); }

@@ -530,5 +530,57 @@ inline PostPlan plan_post(int64_t n_elem, int32_t n_sel, int32_t n_pairs, int n_
   return p;
 }
 
+// ---- oe_sobol_* ---------------------------------------------------------------------
+constexpr int kSobolVar = 3;  // doubles of the variance cell
+constexpr int kSobolCov = 6;  // doubles of a factor cell
+// Workgroups of k_sobol_accum per CU in all.  A run's lanes fold their cells once per column and
+// factor tile whatever its length, and nb is 1/(d + 2) of the chunk's walkers: longer runs than
+// the band's 16 per CU amortise the folds.  The best of 1, 2, 4, 8 and 16 measured (DESIGN.md
+// §3.15: 0.63, 0.63, 0.81, 0.71, 0.71 ms on a 1 GiB chunk of 1000 rows; 1 and 2 give the same runs
+// there, and 2 leaves a short row more workgroups).
+constexpr int kSobolWgPerCu = 2;
+
+// doubles per accumulator cell and per partial of d factors
+constexpr int sobol_cell(int d) { return kSobolVar + kSobolCov * d; }
+
+struct SobolPlan {
+  unsigned grid = 0, block = kBandBlock;  // k_sobol_accum: grid = n_rows * blocks_per_row
+  int64_t per_block = 0;                  // consecutive base rows of one row per workgroup
+  int32_t blocks_per_row = 0;
+  size_t partial_bytes = 0;               // k_sobol_accum's [n_rows][blocks_per_row][n_cols][cell] doubles
+  size_t cell_bytes = 0;                  // one block's cells: [n_rows][n_cols][cell] doubles
+  unsigned init_grid = 0;                 // k_sobol_init: one lane per double of every block's cells
+  unsigned cell_grid = 0;                 // k_sobol_merge: one lane per (row, column, sub-cell), d + 1 sub-cells
+  unsigned finish_grid = 0;               // k_sobol_finish: one lane per (row, column, factor)
+};
+
+// k_sobol_accum over a chunk values [n_rows][n_states][(d + 2) nb]: workgroup (i, j) folds base
+// rows [j * per_block, min(nb, (j + 1) * per_block)) of row i, every group of them.  The base
+// rows are the walkers of this reduction: the run is plan_band_reduce's over nb, for wg_per_cu
+// workgroups per CU in place of its 16.
+inline SobolPlan plan_sobol(int n_rows, int64_t nb, int n_cols, int d, int n_blocks, int n_cu,
+                            int wg_per_cu = kSobolWgPerCu) {
+  SobolPlan p;
+  const BandPlan b = plan_band_reduce(n_rows, nb, 1, std::max(1, n_cu * wg_per_cu / 16));
+  p.per_block = b.per_block;
+  p.blocks_per_row = b.blocks_per_row;
+  p.grid = b.grid;
+  const size_t cells = (size_t)n_rows * (size_t)n_cols;
+  p.cell_bytes = sizeof(double) * (size_t)sobol_cell(d) * cells;
+  p.partial_bytes = p.cell_bytes * (size_t)p.blocks_per_row;
+  p.init_grid = (unsigned)((cells * (size_t)sobol_cell(d) * (size_t)n_blocks + kBlock - 1) / kBlock);
+  p.cell_grid = (unsigned)((cells * (size_t)(d + 1) + kBlock - 1) / kBlock);
+  p.finish_grid = (unsigned)((cells * (size_t)d + kBlock - 1) / kBlock);
+  return p;
+}
+
+// Base rows per chunk of a design of G = d + 2 groups: the largest multiple of 256 whose
+// [T][S][G * nb] doubles fit budget_bytes, at least 256.  A block of base rows is streamed in
+// chunks of this many; only its last chunk may be ragged.
+inline int64_t plan_sobol_chunk(int T, int S, int G, int64_t budget_bytes) {
+  const int64_t per_base = (int64_t)8 * T * S * G;
+  return std::max<int64_t>(256, budget_bytes / per_base / 256 * 256);
+}
+
 }  // namespace plan
 }  // namespace oe

@@ -199,6 +199,42 @@ def band_summary(acc: np.ndarray) -> dict:
             "min": np.where(some, acc[..., 3], nan), "max": np.where(some, acc[..., 4], nan)}
 
 
+def sobol_chunk(n_times: int, n_states: int, n_groups: int, budget_bytes: int = BAND_BUDGET) -> int:
+    """Base rows per trajectory chunk of ``Engine.sobol`` (csrc/launch_plan.h plan_sobol_chunk,
+    restated): the largest multiple of 256 whose [T][S][G * chunk] doubles fit the budget, at
+    least 256."""
+    return max(256, int(budget_bytes) // (8 * int(n_times) * int(n_states) * int(n_groups)) // 256 * 256)
+
+
+def sobol_indices(cells: np.ndarray, n_factors: int) -> dict:
+    """The estimator of ``oe_sobol_finish`` on cells [...][3 + 6 d] (n_V, mean, M2, then per
+    factor n, mx, my, M2x, M2y, Cxy): ``S1``, ``ST``, ``n`` [...][d] and ``n_valid``, ``mean``,
+    ``var`` [...].  NaN where the variance is not positive or a factor has no valid row."""
+    d = int(n_factors)
+    nv, mean, m2 = cells[..., 0], cells[..., 1], cells[..., 2]
+    cov = cells[..., 3:].reshape(cells.shape[:-1] + (d, 6))
+    n, my, m2y, cxy = cov[..., 0], cov[..., 2], cov[..., 4], cov[..., 5]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        var = np.where(nv > 0, m2 / nv, np.nan)
+        ok = (var[..., None] > 0) & (n > 0)
+        s1 = np.where(ok, (cxy / n) / var[..., None], np.nan)
+        st = np.where(ok, ((m2y / n + my * my) / 2.0) / var[..., None], np.nan)
+    return {"S1": s1, "ST": st, "n": n.astype(np.int64), "n_valid": nv.astype(np.int64),
+            "mean": np.where(nv > 0, mean, np.nan), "var": var}
+
+
+def sobol_se(cells: np.ndarray, n_factors: int):
+    """Standard errors by replicates: cells [R][...][3 + 6 d], one per block of base rows ->
+    (S1_se, ST_se) [...][d], the sample standard deviation (R - 1 in the denominator) of the
+    R per-block indices divided by sqrt(R); NaN for R = 1 or where a block's index is NaN."""
+    R = cells.shape[0]
+    per = sobol_indices(cells, n_factors)
+    if R < 2:
+        nan = np.full(per["S1"].shape[1:], np.nan)
+        return nan, nan.copy()
+    return tuple(np.std(per[k], axis=0, ddof=1) / np.sqrt(R) for k in ("S1", "ST"))
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -619,6 +655,97 @@ class Engine:
             res["hist2"] = (hist2_t.cpu().numpy().view(np.uint32) if hist2_t is not None
                             else np.empty((0, int(n_bins2), int(n_bins2)), dtype=np.uint32))
         return res
+
+    # -- Sobol' sensitivity indices -------------------------------------------------------------------
+    def sobol(self, theta_a, theta_b, y0_a, y0_b, factors, log: bool = True, col_masks=None, blocks: int = 8,
+              chunk=None, nt_stores: bool = True):
+        """First-order and total Sobol' indices of every output column per grid time, and of chi,
+        over a Saltelli design (the estimator is stated at ``oe_sobol_begin`` in
+        include/odelib_amd.h).
+
+        ``theta_a``, ``theta_b`` [P][N] and ``y0_a``, ``y0_b`` [S][N]: the two sample matrices of N
+        base rows.  ``factors``: per factor a pair (theta rows, y0 rows) that are taken from B
+        together; the design is N (d + 2) walkers: A, B, and per factor A with its rows from B.
+        ``col_masks``: one state bitmask per column (default: every state its own column);
+        ``log``: the output is the log of the column (rows that are not finite and positive are
+        left out) or the column itself.  chi is always folded as it is.  ``blocks``: replicate
+        blocks of base rows for the standard errors (N must be a multiple).  Each block is
+        streamed in chunks of ``chunk`` base rows (rounded up to a multiple of 64; default
+        ``sobol_chunk``: 1 GiB of trajectory) through ``integrate`` into one reused buffer.
+        Returns host arrays ``S1``, ``ST``, ``S1_se``, ``ST_se``, ``n`` [T][n_cols][d] and
+        ``n_valid``, ``mean``, ``var`` [T][n_cols]; the same for chi under ``chi`` ([d] and
+        scalars); ``status_or`` and ``n_status`` as ``band``."""
+        torch = self.torch
+        pb = self.problem
+        T, S, P = pb.n_times, pb.n_states, pb.n_params
+        ta = theta_a if isinstance(theta_a, torch.Tensor) else np.asarray(theta_a)
+        n_base = int(ta.shape[1])
+        d, R = len(factors), int(blocks)
+        G = d + 2
+        if d < 1:
+            raise ValueError("sobol needs at least one factor")
+        if R < 1 or n_base < 1 or n_base % R:
+            raise ValueError(f"n_base ({n_base}) must be a positive multiple of blocks ({R})")
+        theta_a, theta_b = self._dev(theta_a, (P, n_base)), self._dev(theta_b, (P, n_base))
+        y0_a, y0_b = self._dev(y0_a, (S, n_base)), self._dev(y0_b, (S, n_base))
+        rows = [(torch.as_tensor(np.asarray(tr, dtype=np.int64).reshape(-1), device=self.dev),
+                 torch.as_tensor(np.asarray(yr, dtype=np.int64).reshape(-1), device=self.dev)) for tr, yr in factors]
+        masks = np.asarray([1 << s for s in range(S)] if col_masks is None else col_masks, dtype=np.uint64)
+        n_cols = len(masks)
+        per = n_base // R
+        nbc = sobol_chunk(T, S, G) if chunk is None else -(-max(int(chunk), 1) // 64) * 64
+        nbc = min(nbc, per)
+        cell = N.sobol_cell(d)
+        f64 = torch.float64
+        buf = torch.empty(T * S * G * nbc, dtype=f64, device=self.dev)
+        acc = torch.empty((R, T, n_cols, cell), dtype=f64, device=self.dev)
+        acc_chi = torch.empty((R, 1, 1, cell), dtype=f64, device=self.dev)
+        idx = torch.empty((T, n_cols, d, 3), dtype=f64, device=self.dev)
+        out = torch.empty((T, n_cols, 3), dtype=f64, device=self.dev)
+        idx_chi = torch.empty((1, 1, d, 3), dtype=f64, device=self.dev)
+        out_chi = torch.empty((1, 1, 3), dtype=f64, device=self.dev)
+        status_all = torch.empty(G * n_base, dtype=torch.int32, device=self.dev)  # folded once, after the loop
+        self._sync_stream()
+        targs = self.ctx.sobol_args(T, S, masks, d, n_base, log, R)
+        cargs = self.ctx.sobol_args(1, 1, [1], d, n_base, False, R)
+        self.ctx.sobol_begin(targs, _ptr(acc), N.OE_ASYNC)
+        self.ctx.sobol_begin(cargs, _ptr(acc_chi), N.OE_ASYNC)
+
+        def design(m_a, m_b, a, b, which):
+            """[rows][G][nb]: A, B, then per factor A with that factor's rows from B"""
+            m = m_a[:, a:b].repeat(1, G).view(m_a.shape[0], G, b - a)
+            m[:, 1, :] = m_b[:, a:b]
+            for i, r in enumerate(rows):
+                if r[which].numel():
+                    m[r[which], 2 + i, :] = m_b[r[which], a:b]
+            return m.view(m_a.shape[0], G * (b - a))
+
+        for r in range(R):
+            for a in range(r * per, (r + 1) * per, nbc):
+                b = min(a + nbc, (r + 1) * per)
+                w = G * (b - a)
+                th, y0 = design(theta_a, theta_b, a, b, 0), design(y0_a, y0_b, a, b, 1)
+                traj = buf[:T * S * w].view(T, S, w)
+                res = self.integrate(y0, th, traj_out=traj, nt_stores=nt_stores, sync=False, timing=False)
+                status_all[G * a:G * b] = res["status"]
+                self.ctx.sobol_accum(targs, r, b - a, _ptr(traj), _ptr(acc), N.OE_ASYNC)
+                self.ctx.sobol_accum(cargs, r, b - a, _ptr(res["chi"]), _ptr(acc_chi), N.OE_ASYNC)
+        self.ctx.sobol_finish(targs, _ptr(acc), _ptr(idx), _ptr(out), N.OE_ASYNC)
+        self.ctx.sobol_finish(cargs, _ptr(acc_chi), _ptr(idx_chi), _ptr(out_chi), N.OE_ASYNC)
+        status = (sum(((status_all & bit) != 0).any().to(torch.int32) * bit for bit in (1, 2, 4, 8, 16)),
+                  (status_all != 0).sum())
+        torch.cuda.synchronize(self.dev)
+
+        def result(idx, out, acc):
+            ix, o = idx.cpu().numpy(), out.cpu().numpy()
+            res = {"S1": ix[..., 0].copy(), "ST": ix[..., 1].copy(), "n": ix[..., 2].astype(np.int64),
+                   "n_valid": o[..., 0].astype(np.int64), "mean": o[..., 1].copy(), "var": o[..., 2].copy()}
+            res["S1_se"], res["ST_se"] = sobol_se(acc.cpu().numpy(), d)
+            return res
+
+        res = result(idx, out, acc)
+        res["chi"] = {k: v[0, 0] for k, v in result(idx_chi, out_chi, acc_chi).items()}
+        return self._status_result(res, status)
 
     def last_kernel_ms(self) -> float:
         return self.ctx.last_kernel_ms()

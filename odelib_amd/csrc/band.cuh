@@ -7,7 +7,7 @@
 //   k_band_moments + k_band_merge   (n, mean ℓ, M2 ℓ, min C, max C) per (grid row, column)
 //   k_band_hist                     uint32 histogram of ℓ on [log min, log max], B bins
 //   k_band_quantiles                quantiles of C from the histogram
-// The two passes over the chunk are tiled by reduce.cuh's walker runs, one grid row and run per
+// The two passes over the chunk are tiled by tiling.h's runs of walkers, one grid row and run per
 // workgroup.  The columns are the outer loop: the registers and the LDS hold one column at a
 // time, so neither depends on the column count, and disjoint masks read every state once.
 // Floating-point merges run in reduce.cuh's fixed order, so the moments are the same bits run
@@ -21,7 +21,6 @@ namespace oe {
 constexpr int kBandMaxBins = 4096;  // k_band_hist's LDS histogram (one column at a time)
 constexpr int kBandMaxCols = 64;
 constexpr int kBandMaxQ = 64;
-constexpr int kBandAcc = 5;         // doubles per accumulator cell: n, mean, M2, min, max
 
 struct BandArgs {
   const double* traj;     // [T][S][W]
@@ -82,7 +81,7 @@ __device__ __forceinline__ void band_init(double* __restrict__ acc, int64_t n_ce
 
 __device__ __forceinline__ void band_moments(const BandArgs& a) {
   __shared__ Mom s_wave[kBandBlock / 64];
-  const WalkerRun run = walker_run(a.bpr, a.per_block, a.W);
+  const Run run = run_of(blockIdx.x, a.bpr, a.per_block, a.W);
   const double* row = a.traj + (int64_t)run.row * a.S * a.W;
   const cptr<uint64_t> masks = kconst(a.masks);
   for (int c = 0; c < a.n_cols; ++c) {
@@ -115,7 +114,7 @@ __device__ __forceinline__ int band_bin(double l, double lo, double wbin, int B,
 
 __device__ __forceinline__ void band_hist(const BandArgs& a) {
   __shared__ uint32_t s_h[kBandMaxBins];
-  const WalkerRun run = walker_run(a.bpr, a.per_block, a.W);
+  const Run run = run_of(blockIdx.x, a.bpr, a.per_block, a.W);
   const int i = run.row, t = threadIdx.x, B = a.n_bins;
   const double* row = a.traj + (int64_t)i * a.S * a.W;
   const cptr<uint64_t> masks = kconst(a.masks);

@@ -53,19 +53,19 @@ const Entry* find_entry(int32_t model_id, int32_t S) {
   return nullptr;
 }
 
-using plan::kBlock;
 using plan::kMaxWalkers;
-// launch_plan.h restates the device headers' constants (it includes none of them)
+// launch_plan.h restates the integrate and MH headers' constants (it includes no device header; the
+// analysis kernels' are tiling.h's, defined once), and the public header restates sobol_cell
 static_assert(plan::kPipeWalkers == kPipeWalkers && plan::kStiffRegS == kStiffRegS &&
                   plan::kHandBdfWaves == kHandBdfWaves && plan::kResolveLdsDepth == kResolveLdsDepth &&
-                  plan::kBlock == kMhBlock && plan::kBandBlock == kBandBlock && plan::kBandTile == kBandTile &&
-                  plan::kDiagBlock == kDiagBlock && plan::kDiagLB == kDiagLB && plan::kDiagPart == kDiagPart &&
-                  plan::kDiagState == kDiagState && plan::kWaicAcc == kWaicAcc && plan::kLooBits == kLooBits &&
-                  plan::kLooPasses == kLooPasses && plan::kLooState == kLooState && plan::kLooAcc == kLooAcc &&
-                  plan::kLooTailMax == kLooTailMax && plan::kLooFitBlock == kLooFitBlock &&
-                  plan::kPostMarg == kPostMarg && plan::kPostPair == kPostPair &&
-                  plan::kSobolVar == kSobolVar && plan::kSobolCov == kSobolCov && OE_SOBOL_CELL(7) == sobol_cell(7),
-              "launch_plan.h and the kernels disagree");
+                  kBlock == kMhBlock && OE_SOBOL_CELL(7) == sobol_cell(7),
+              "launch_plan.h, tiling.h or the public header and the kernels disagree");
+
+// an integer environment override (measurements), 0 when unset; each caller reads its own once
+long env_override(const char* name) {
+  const char* v = getenv(name);
+  return v ? strtol(v, nullptr, 10) : 0;
+}
 
 // what the plans need to know of a model: which slots its Entry fills
 plan::ModelCaps caps_of(const Entry* e, int P) {
@@ -269,10 +269,7 @@ struct DeviceGuard {
 
 // the XCD run length of the one-lane kernels: 512 walkers, or OE_XCD_RUN_WALKERS (measurements)
 int64_t xcd_run_walkers() {
-  static const long n = [] {
-    const char* v = getenv("OE_XCD_RUN_WALKERS");
-    return v ? strtol(v, nullptr, 10) : 0;
-  }();
+  static const long n = env_override("OE_XCD_RUN_WALKERS");
   return n > 0 ? (int64_t)n : (int64_t)512;
 }
 
@@ -1070,10 +1067,7 @@ int device_args(oe_ctx* c, const char* who, uint32_t flags, int64_t W = 1) {
 
 // workgroups of the reduce passes per CU: 16, or OE_BAND_WG_PER_CU (measurements)
 int band_cus(const oe_ctx* c) {
-  static const long n = [] {
-    const char* v = getenv("OE_BAND_WG_PER_CU");
-    return v ? strtol(v, nullptr, 10) : 0;
-  }();
+  static const long n = env_override("OE_BAND_WG_PER_CU");
   return n > 0 ? (int)std::max<long>(1, (long)c->n_cu * n / 16) : c->n_cu;
 }
 
@@ -1259,10 +1253,7 @@ namespace {
 
 // workgroups of the streaming passes per CU and row: 2, or OE_POST_WG_PER_CU (measurements)
 int post_wg_per_cu() {
-  static const long n = [] {
-    const char* v = getenv("OE_POST_WG_PER_CU");
-    return v ? strtol(v, nullptr, 10) : 0;
-  }();
+  static const long n = env_override("OE_POST_WG_PER_CU");
   return n > 0 ? (int)std::min<long>(n, 64) : plan::kPostWgPerCu;
 }
 
@@ -1412,7 +1403,7 @@ int oe_waic_accum(oe_ctx* c, int64_t W, const double* traj, double* acc, double*
   a.w_offset = terms ? w_offset : 0;
   a.W = W;
   a.per_block = pl.per_block;
-  a.bpo = pl.blocks_per_obs;
+  a.bpo = pl.blocks_per_row;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, launch(kernel_of(k_waic_accum), dim3(pl.grid), dim3(pl.block), c->stream, a));
   OE_HIP(c, launch(kernel_of(k_waic_merge), dim3(pl.cell_grid), dim3(kBlock), c->stream, a));
@@ -1454,7 +1445,7 @@ int oe_loo_run(oe_ctx* c, const oe_loo_args* g, uint32_t flags) {
     return fail(c, pl.error,
                 "oe_loo_run: the tail of " + std::to_string(g->n_rows) + " rows, " +
                     std::to_string(plan::loo_tail_len(g->n_rows, g->r_eff)) + " elements, exceeds the limit of " +
-                    std::to_string(plan::kLooTailMax) + " (r_eff = 1: at most 7456540 rows)");
+                    std::to_string(kLooTailMax) + " (r_eff = 1: at most 7456540 rows)");
   OE_DEVICE_GUARD(c);
   rc = c->loo.reserve(c, pl.bytes);
   if (rc) return rc;
@@ -1478,7 +1469,7 @@ int oe_loo_run(oe_ctx* c, const oe_loo_args* g, uint32_t flags) {
   a.terms_ld = g->terms_ld;
   a.per_block = pl.per_block;
   a.n_obs = g->n_obs;
-  a.bpo = pl.blocks_per_obs;
+  a.bpo = pl.blocks_per_row;
   a.tail_cap = pl.tail_cap;
   OE_HIP(c, hipEventRecord(c->ev0, c->stream));
   OE_HIP(c, hipMemcpyAsync(base + pl.off_c, c->loo_c.data(), sizeof(double) * (size_t)g->n_obs, hipMemcpyHostToDevice,
@@ -1501,10 +1492,7 @@ namespace {
 
 // workgroups of k_sobol_accum per CU: launch_plan.h's, or OE_SOBOL_WG_PER_CU (measurements)
 int sobol_wg_per_cu() {
-  static const long n = [] {
-    const char* v = getenv("OE_SOBOL_WG_PER_CU");
-    return v ? strtol(v, nullptr, 10) : 0;
-  }();
+  static const long n = env_override("OE_SOBOL_WG_PER_CU");
   return n > 0 ? (int)std::min<long>(n, 64) : plan::kSobolWgPerCu;
 }
 

@@ -31,12 +31,8 @@
 
 namespace oe {
 
-constexpr int kDiagBlock = 256;   // threads (chains) per workgroup
-constexpr int kDiagLB = 16;       // lags per pass: 2·16 accumulator + 2·16 window VGPR pairs
 constexpr int kDiagMaxRows = 64;
 constexpr int kDiagSummary = 12;  // doubles per row of the summary
-constexpr int kDiagPart = 4;      // doubles per moments partial: M, m̄, Σ(m_j − m̄)², mean s_j²
-constexpr int kDiagState = 4;     // doubles of the walk's state per row: next pair, P', ΣP', unused
 
 enum { DG_NCHAINS, DG_N, DG_MEAN, DG_W, DG_B, DG_VARP, DG_RHAT, DG_TAU, DG_ESS, DG_MCSE, DG_STOP, DG_TRUNC };
 

@@ -1,15 +1,17 @@
-// launch_plan.h — what oe_integrate, oe_mh_run, the oe_band_* passes, oe_diag_run, oe_post_run, the
-// oe_waic_* passes and oe_loo_run launch, decided by pure functions: numbers in, a plan out (kernel, grids, half
-// waves, XCD runs, the hand-over queue's placement, speculation depth, chunk, lag blocks, walker
-// runs, buffer sizes).  No HIP here, so tests/sanitize/plan_driver.cpp, band_plan_driver.cpp,
-// diag_plan_driver.cpp, post_plan_driver.cpp, waic_plan_driver.cpp and loo_plan_driver.cpp check the arithmetic on the CPU;
-// capi.hip reserves, fills the arguments and launches.
+// launch_plan.h — what every entry point of the C-ABI launches (oe_integrate, oe_mh_run and the
+// analysis passes: bands, diagnostics, WAIC, PSIS-LOO, posterior summaries, Sobol' indices),
+// decided by pure functions: numbers in, a plan out (kernel, grids, half waves, XCD runs, the
+// hand-over queue's placement, speculation depth, chunk, lag blocks, runs, buffer sizes).  No HIP
+// here, so the plan drivers under tests/sanitize check the arithmetic on the CPU; capi.hip
+// reserves, fills the arguments and launches.  The analysis kernels' tiling and the sizes they
+// share with their plans are tiling.h's.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/odelib_amd.h"
+#include "tiling.h"
 
 #ifndef OE_LANE_INTEGRATE  // as ode_kernels.cuh (measurement builds)
 #define OE_LANE_INTEGRATE 0
@@ -27,8 +29,10 @@
 namespace oe {
 namespace plan {
 
-// the device headers' constants (capi.hip asserts that they agree)
-constexpr int kBlock = 256;
+using namespace oe;  // tiling.h's names, for whoever uses this namespace
+
+// the integrate and MH headers' constants (capi.hip asserts that they agree, and holds tiling.h's
+// kBlock to kMhBlock)
 constexpr int kPipeWalkers = 256;     // walkers per workgroup of the piped RK4 kernels
 constexpr int kStiffRegS = 8;
 constexpr int kHandBdfWaves = OE_HQ_WAVES;
@@ -302,16 +306,23 @@ inline MhRound plan_mh_round(const MhPlan& p, int64_t W, int n_cu, int it0, int 
   return r;
 }
 
+// One scratch buffer in parts: take(n) is the byte offset of the next part of n bytes, a multiple
+// of 256; bytes, the total so far
+struct Scratch {
+  size_t bytes = 0;
+  size_t take(size_t n) {
+    const size_t off = bytes;
+    bytes += (n + 255) / 256 * 256;
+    return off;
+  }
+};
+
 // ---- oe_band_* ----------------------------------------------------------------------
-constexpr int kBandBlock = 256;                        // threads per workgroup of the reduce passes
-constexpr int kBandTile = 1024;                        // walkers per workgroup trip (4 per lane)
 constexpr int64_t kBandBudget = int64_t(1) << 30;      // default resident trajectory chunk: 1 GiB
 
-struct BandPlan {
+struct BandPlan : RowRuns {  // the runs of the walkers of one grid row
   unsigned grid = 0, block = kBandBlock;  // k_band_moments / k_band_hist: grid = T * blocks_per_row
-  int64_t per_block = 0;                  // consecutive walkers of one grid row per workgroup
-  int32_t blocks_per_row = 0;
-  size_t partial_bytes = 0;               // k_band_moments' [T][blocks_per_row][n_cols][5] doubles
+  size_t partial_bytes = 0;               // k_band_moments' [T][blocks_per_row][n_cols][kBandAcc] doubles
   unsigned cell_grid = 0;                 // k_band_init / k_band_merge: one lane per (row, column)
 };
 
@@ -320,14 +331,9 @@ struct BandPlan {
 // all (enough rows: one workgroup per row), runs a multiple of kBandTile.
 inline BandPlan plan_band_reduce(int T, int64_t W, int n_cols, int n_cu) {
   BandPlan p;
-  const int64_t tiles = (W + kBandTile - 1) / kBandTile;
-  const int64_t want = std::max<int64_t>(1, ((int64_t)16 * n_cu + T - 1) / T);
-  const int64_t bpr0 = std::min(tiles, want);
-  const int64_t tiles_per_block = (tiles + bpr0 - 1) / bpr0;
-  p.per_block = tiles_per_block * kBandTile;
-  p.blocks_per_row = (int32_t)((tiles + tiles_per_block - 1) / tiles_per_block);
+  static_cast<RowRuns&>(p) = row_runs(W, std::max<int64_t>(1, ((int64_t)16 * n_cu + T - 1) / T));
   p.grid = (unsigned)((int64_t)T * p.blocks_per_row);
-  p.partial_bytes = sizeof(double) * 5 * (size_t)T * (size_t)p.blocks_per_row * (size_t)n_cols;
+  p.partial_bytes = sizeof(double) * kBandAcc * (size_t)T * (size_t)p.blocks_per_row * (size_t)n_cols;
   p.cell_grid = (unsigned)(((int64_t)T * n_cols + kBlock - 1) / kBlock);
   return p;
 }
@@ -344,13 +350,9 @@ inline int64_t plan_band_chunk(int T, int S, int64_t W_total, int64_t budget_byt
 }
 
 // ---- oe_waic_* ----------------------------------------------------------------------
-constexpr int kWaicAcc = 5;  // doubles per accumulator cell and per partial
-
-struct WaicPlan {
-  unsigned grid = 0, block = kBandBlock;  // k_waic_accum: grid = n_obs * blocks_per_obs
-  int64_t per_block = 0;                  // consecutive walkers of one observation per workgroup
-  int32_t blocks_per_obs = 0;
-  size_t partial_bytes = 0;               // k_waic_accum's [n_obs][blocks_per_obs][5] doubles
+struct WaicPlan : RowRuns {  // the runs of the walkers of one observation record
+  unsigned grid = 0, block = kBandBlock;  // k_waic_accum: grid = n_obs * blocks_per_row
+  size_t partial_bytes = 0;               // k_waic_accum's [n_obs][blocks_per_row][kWaicAcc] doubles
   unsigned cell_grid = 0;                 // k_waic_init / k_waic_merge: one lane per observation
   unsigned finish_grid = 1, finish_block = kBlock;  // k_waic_finish: one workgroup, lanes strided
 };
@@ -362,23 +364,14 @@ struct WaicPlan {
 inline WaicPlan plan_waic(int n_obs, int64_t W, int n_cu) {
   WaicPlan p;
   const BandPlan b = plan_band_reduce(n_obs, W, 1, n_cu);
-  p.per_block = b.per_block;
-  p.blocks_per_obs = b.blocks_per_row;
+  static_cast<RowRuns&>(p) = b;
   p.grid = b.grid;
-  p.partial_bytes = sizeof(double) * kWaicAcc * (size_t)n_obs * (size_t)p.blocks_per_obs;
+  p.partial_bytes = sizeof(double) * kWaicAcc * (size_t)n_obs * (size_t)p.blocks_per_row;
   p.cell_grid = (unsigned)(((int64_t)n_obs + kBlock - 1) / kBlock);
   return p;
 }
 
 // ---- oe_loo_run ---------------------------------------------------------------------
-constexpr int kLooBits = 11;          // a digit of the radix select
-constexpr int kLooBins = 1 << kLooBits;
-constexpr int kLooPasses = 6;         // digit passes: 6 x 11 bits cover a term's 64
-constexpr int kLooState = 8;          // 64-bit words of the select's state per observation
-constexpr int kLooAcc = 7;            // doubles per gather cell and per partial
-constexpr int kLooTailMax = 8192;     // doubles of the tail k_loo_fit holds in LDS
-constexpr int kLooFitBlock = 256;
-
 // the tail length M = ceil(min(N/5, 3 sqrt(N / r_eff))) of N valid rows (loo.cuh: the same
 // expression on the device); not decreasing in N
 inline int64_t loo_tail_len(int64_t N, double r_eff) {
@@ -386,11 +379,9 @@ inline int64_t loo_tail_len(int64_t N, double r_eff) {
   return (int64_t)std::ceil(std::min(n / 5.0, 3.0 * std::sqrt(n / r_eff)));
 }
 
-struct LooPlan {
+struct LooPlan : RowRuns {  // the runs of the rows of one observation
   int error = OE_OK;                      // OE_ERR_ARG: the tail of n_rows valid rows exceeds kLooTailMax
-  unsigned grid = 0, block = kBandBlock;  // k_loo_select / k_loo_gather: grid = n_obs * blocks_per_obs
-  int64_t per_block = 0;                  // consecutive rows of one observation per workgroup
-  int32_t blocks_per_obs = 0;
+  unsigned grid = 0, block = kBandBlock;  // k_loo_select / k_loo_gather: grid = n_obs * blocks_per_row
   unsigned obs_grid = 0;                  // k_loo_pick / k_loo_fit: one workgroup of kLooFitBlock per observation
   unsigned cell_grid = 0;                 // k_loo_merge: one lane per observation
   int32_t tail_cap = 0;                   // doubles per observation of the tail buffer, >= M of any N <= n_rows
@@ -398,7 +389,7 @@ struct LooPlan {
   // [0, zero_bytes) (the counts and the state) is zeroed before the first pass
   size_t off_hist = 0;    // [n_obs][kLooBins] uint32
   size_t off_state = 0;   // [n_obs][kLooState] uint64
-  size_t off_part = 0;    // [n_obs][blocks_per_obs][kLooAcc] doubles
+  size_t off_part = 0;    // [n_obs][blocks_per_row][kLooAcc] doubles
   size_t off_acc = 0;     // [n_obs][kLooAcc] doubles
   size_t off_tail = 0;    // [n_obs][tail_cap] doubles
   size_t off_c = 0;       // [n_obs] doubles: c_o
@@ -420,32 +411,24 @@ inline LooPlan plan_loo(int n_obs, int64_t n_rows, double r_eff, int n_cu) {
   }
   p.tail_cap = (int32_t)std::max<int64_t>(1, m_max);
   const BandPlan b = plan_band_reduce(n_obs, n_rows, 1, n_cu);
-  p.per_block = b.per_block;
-  p.blocks_per_obs = b.blocks_per_row;
+  static_cast<RowRuns&>(p) = b;
   p.grid = b.grid;
   p.obs_grid = (unsigned)n_obs;
   p.cell_grid = (unsigned)(((int64_t)n_obs + kBlock - 1) / kBlock);
-  auto part = [&p](size_t& off, size_t bytes) {
-    off = p.bytes;
-    p.bytes += (bytes + 255) / 256 * 256;
-  };
+  Scratch s;
   const size_t rows = (size_t)n_obs;
-  part(p.off_hist, sizeof(uint32_t) * rows * kLooBins);
-  part(p.off_state, sizeof(uint64_t) * rows * kLooState);
-  p.zero_bytes = p.bytes;
-  part(p.off_part, sizeof(double) * rows * (size_t)p.blocks_per_obs * kLooAcc);
-  part(p.off_acc, sizeof(double) * rows * kLooAcc);
-  part(p.off_tail, sizeof(double) * rows * (size_t)p.tail_cap);
-  part(p.off_c, sizeof(double) * rows);
+  p.off_hist = s.take(sizeof(uint32_t) * rows * kLooBins);
+  p.off_state = s.take(sizeof(uint64_t) * rows * kLooState);
+  p.zero_bytes = s.bytes;
+  p.off_part = s.take(sizeof(double) * rows * (size_t)p.blocks_per_row * kLooAcc);
+  p.off_acc = s.take(sizeof(double) * rows * kLooAcc);
+  p.off_tail = s.take(sizeof(double) * rows * (size_t)p.tail_cap);
+  p.off_c = s.take(sizeof(double) * rows);
+  p.bytes = s.bytes;
   return p;
 }
 
 // ---- oe_diag_run --------------------------------------------------------------------
-constexpr int kDiagBlock = 256;  // chains per workgroup (one lane per chain)
-constexpr int kDiagLB = 16;      // lags per pass of k_diag_acov
-constexpr int kDiagPart = 4;     // doubles per moments partial
-constexpr int kDiagState = 4;    // doubles of the walk's state per row
-
 struct DiagPlan {
   int32_t n = 0;                           // draws per split chain, K div 2
   int32_t max_lag = 0;                     // resolved: 0 means n - 1
@@ -475,31 +458,25 @@ inline DiagPlan plan_diag(int32_t K, int64_t W, int32_t n_sel, int32_t max_lag) 
   p.grid = (unsigned)((int64_t)n_sel * p.blocks_per_row);
   p.row_grid = (unsigned)n_sel;
   p.lag_blocks = (p.max_lag + kDiagLB - 1) / kDiagLB;
-  auto part = [&p](size_t& off, size_t bytes) {
-    off = p.bytes;
-    p.bytes += (bytes + 255) / 256 * 256;
-  };
+  Scratch s;
   const size_t rows = (size_t)n_sel, bpr = (size_t)p.blocks_per_row;
-  part(p.off_cmean, sizeof(double) * rows * 2 * (size_t)W);
-  part(p.off_mpart, sizeof(double) * rows * bpr * kDiagPart);
-  part(p.off_apart, sizeof(double) * rows * bpr * kDiagLB);
-  part(p.off_acov, sizeof(double) * rows * (size_t)(p.max_lag + 1));
-  part(p.off_state, sizeof(double) * rows * kDiagState);
-  part(p.off_done, sizeof(int32_t) * rows);
+  p.off_cmean = s.take(sizeof(double) * rows * 2 * (size_t)W);
+  p.off_mpart = s.take(sizeof(double) * rows * bpr * kDiagPart);
+  p.off_apart = s.take(sizeof(double) * rows * bpr * kDiagLB);
+  p.off_acov = s.take(sizeof(double) * rows * (size_t)(p.max_lag + 1));
+  p.off_state = s.take(sizeof(double) * rows * kDiagState);
+  p.off_done = s.take(sizeof(int32_t) * rows);
+  p.bytes = s.bytes;
   return p;
 }
 
 // ---- oe_post_run --------------------------------------------------------------------
-constexpr int kPostMarg = 5;         // doubles per row of marg and per moments partial
-constexpr int kPostPair = 6;         // doubles per pair cell and per pair partial
 constexpr int kPostWgPerCu = 2;      // workgroups per CU and row (or pair): the best of 2, 4, 8, 16 measured
 
-struct PostPlan {
+struct PostPlan : RowRuns {  // the runs of the elements e = k*W + w of one row, <= 2^30 each
   unsigned block = kBandBlock;
   unsigned row_grid = 0;    // k_post_moments / k_post_hist: n_sel * blocks_per_row
   unsigned pair_grid = 0;   // k_post_pairs: n_pairs * blocks_per_row
-  int64_t per_block = 0;    // consecutive elements e = k*W + w of one row per workgroup, <= 2^30
-  int32_t blocks_per_row = 0;
   // the scratch, one buffer: byte offsets of its parts (each a multiple of 256) and the total
   size_t off_mpart = 0;     // [n_sel][blocks_per_row][kPostMarg] doubles
   size_t off_ppart = 0;     // [n_pairs][blocks_per_row][kPostPair] doubles
@@ -512,27 +489,18 @@ struct PostPlan {
 // not on what else is selected: a row's bits do not depend on its company.
 inline PostPlan plan_post(int64_t n_elem, int32_t n_sel, int32_t n_pairs, int n_cu, int wg_per_cu = kPostWgPerCu) {
   PostPlan p;
-  const int64_t tiles = (n_elem + kBandTile - 1) / kBandTile;
-  const int64_t want = std::max<int64_t>(4, (int64_t)wg_per_cu * n_cu);  // (at least 4: a run fits 2^30)
-  const int64_t bpr0 = std::min(tiles, want);
-  const int64_t tiles_per_block = (tiles + bpr0 - 1) / bpr0;
-  p.per_block = tiles_per_block * kBandTile;
-  p.blocks_per_row = (int32_t)((tiles + tiles_per_block - 1) / tiles_per_block);
+  static_cast<RowRuns&>(p) = row_runs(n_elem, std::max<int64_t>(4, (int64_t)wg_per_cu * n_cu));  // (at least 4: a run fits 2^30)
   p.row_grid = (unsigned)((int64_t)n_sel * p.blocks_per_row);
   p.pair_grid = (unsigned)((int64_t)n_pairs * p.blocks_per_row);
-  auto part = [&p](size_t& off, size_t bytes) {
-    off = p.bytes;
-    p.bytes += (bytes + 255) / 256 * 256;
-  };
+  Scratch s;
   const size_t bpr = (size_t)p.blocks_per_row;
-  part(p.off_mpart, sizeof(double) * (size_t)n_sel * bpr * kPostMarg);
-  part(p.off_ppart, sizeof(double) * (size_t)n_pairs * bpr * kPostPair);
+  p.off_mpart = s.take(sizeof(double) * (size_t)n_sel * bpr * kPostMarg);
+  p.off_ppart = s.take(sizeof(double) * (size_t)n_pairs * bpr * kPostPair);
+  p.bytes = s.bytes;
   return p;
 }
 
 // ---- oe_sobol_* ---------------------------------------------------------------------
-constexpr int kSobolVar = 3;  // doubles of the variance cell
-constexpr int kSobolCov = 6;  // doubles of a factor cell
 // Workgroups of k_sobol_accum per CU in all.  A run's lanes fold their cells once per column and
 // factor tile whatever its length, and nb is 1/(d + 2) of the chunk's walkers: longer runs than
 // the band's 16 per CU amortise the folds.  The best of 1, 2, 4, 8 and 16 measured (DESIGN.md
@@ -540,13 +508,8 @@ constexpr int kSobolCov = 6;  // doubles of a factor cell
 // there, and 2 leaves a short row more workgroups).
 constexpr int kSobolWgPerCu = 2;
 
-// doubles per accumulator cell and per partial of d factors
-constexpr int sobol_cell(int d) { return kSobolVar + kSobolCov * d; }
-
-struct SobolPlan {
+struct SobolPlan : RowRuns {  // the runs of the base rows of one row
   unsigned grid = 0, block = kBandBlock;  // k_sobol_accum: grid = n_rows * blocks_per_row
-  int64_t per_block = 0;                  // consecutive base rows of one row per workgroup
-  int32_t blocks_per_row = 0;
   size_t partial_bytes = 0;               // k_sobol_accum's [n_rows][blocks_per_row][n_cols][cell] doubles
   size_t cell_bytes = 0;                  // one block's cells: [n_rows][n_cols][cell] doubles
   unsigned init_grid = 0;                 // k_sobol_init: one lane per double of every block's cells
@@ -562,8 +525,7 @@ inline SobolPlan plan_sobol(int n_rows, int64_t nb, int n_cols, int d, int n_blo
                             int wg_per_cu = kSobolWgPerCu) {
   SobolPlan p;
   const BandPlan b = plan_band_reduce(n_rows, nb, 1, std::max(1, n_cu * wg_per_cu / 16));
-  p.per_block = b.per_block;
-  p.blocks_per_row = b.blocks_per_row;
+  static_cast<RowRuns&>(p) = b;
   p.grid = b.grid;
   const size_t cells = (size_t)n_rows * (size_t)n_cols;
   p.cell_bytes = sizeof(double) * (size_t)sobol_cell(d) * cells;

@@ -24,15 +24,9 @@
 
 namespace oe {
 
-constexpr int kLooBits = 11;                 // a digit of the select
-constexpr int kLooBins = 1 << kLooBits;
-constexpr int kLooPasses = 6;                // 6 x 11 bits cover the 64 of a term
-constexpr int kLooState = 8;                 // 64-bit words of the select's state per observation
-constexpr int kLooAcc = 7;                   // doubles per cell: Lse of -t, body Σ exp(x), body count
-constexpr int kLooPoint = 7;                 // n, lppd, elpd_loo, p_loo, pareto_k, n_tail, cutoff
+// (the select's digits, its state, the cell and the tail's sizes: tiling.h)
+constexpr int kLooPoint = 7;                // n, lppd, elpd_loo, p_loo, pareto_k, n_tail, cutoff
 constexpr int kLooSummary = 8;               // n_obs_used, elpd_loo, p_loo, looic, se_elpd, n_k_high, k_max, n_rows_min
-constexpr int kLooTailMax = 8192;            // doubles of the tail k_loo_fit holds in LDS
-constexpr int kLooFitBlock = 256;
 constexpr int kLooMaxCand = 128;             // m = 30 + floor(sqrt(n_tail)) <= 120
 constexpr int kLooCandStep = 4;              // candidates k_loo_fit sums per walk of the tail
 constexpr double kLooKHigh = 0.7;            // pareto_k above this: the observation dominates its estimate
@@ -80,17 +74,17 @@ __device__ __forceinline__ double loo_xcut(const unsigned long long* st, double 
 
 // the rows of the workgroup's run, kBandUnroll loads in flight per lane: f(key) in row order
 template <class F>
-__device__ __forceinline__ void loo_for_each(const double* __restrict__ row, const WalkerRun& r, F f) {
-  for (int64_t w = r.w0 + threadIdx.x; w < r.w1; w += kBandTile) {
+__device__ __forceinline__ void loo_for_each(const double* __restrict__ row, const Run& r, F f) {
+  for_each_trip(threadIdx.x, r, [&](int64_t w) {
     double v[kBandUnroll];
 #pragma unroll
     for (int u = 0; u < kBandUnroll; ++u) {
-      const int64_t wu = w + (int64_t)u * kBandBlock;
-      v[u] = wu < r.w1 ? row[wu] : __builtin_nan("");
+      const int64_t wu = trip_elem(w, u);
+      v[u] = wu < r.hi ? row[wu] : __builtin_nan("");
     }
 #pragma unroll
     for (int u = 0; u < kBandUnroll; ++u) f(loo_key(v[u]));
-  }
+  });
 }
 
 // One digit pass: the valid terms that carry the prefix chosen so far, counted by their next digit.
@@ -98,7 +92,7 @@ __device__ __forceinline__ void loo_select(const LooArgs& a) {
   __shared__ uint32_t s_h[kLooBins];
   __shared__ unsigned long long s_max;
   const int t = threadIdx.x;
-  const WalkerRun run = walker_run(a.bpo, a.per_block, a.n_rows);
+  const Run run = run_of(blockIdx.x, a.bpo, a.per_block, a.n_rows);
   const int o = run.row;
   const unsigned long long* st = a.st + (int64_t)o * kLooState;
   const bool first = a.pass == 0;
@@ -225,7 +219,7 @@ __device__ __forceinline__ Sum2 shifted(const Sum2& x) {
 
 __device__ __forceinline__ void loo_gather(const LooArgs& a) {
   __shared__ LooCell s_wave[kBandBlock / 64];
-  const WalkerRun run = walker_run(a.bpo, a.per_block, a.n_rows);
+  const Run run = run_of(blockIdx.x, a.bpo, a.per_block, a.n_rows);
   const int o = run.row;
   unsigned long long* st = a.st + (int64_t)o * kLooState;
   const double top = __longlong_as_double((long long)st[kLooMax]);

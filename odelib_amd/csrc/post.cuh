@@ -31,8 +31,6 @@ constexpr int kPostMaxQ = 16;
 constexpr int kPostMaxPairs = 120;
 constexpr int kPostMaxBins = kBandMaxBins;  // k_post_hist's LDS histogram
 constexpr int kPostMaxBins2 = 64;           // k_post_pairs' LDS histogram: 64 x 64 uint32
-constexpr int kPostMarg = kBandAcc;         // doubles per row of marg: n, mean, M2, min, max
-constexpr int kPostPair = 6;                // doubles per pair cell: n, mean_x, mean_y, M2x, M2y, Cxy
 
 struct PostArgs {
   const double* samples;  // [K][R_tot][W]
@@ -69,43 +67,25 @@ __device__ __forceinline__ double post_uniform(double v) {
                           __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// workgroup blockIdx.x: row (or pair) blockIdx.x div bpr, the j-th run [e0, e1) of its elements
-struct PostRun {
-  int row, j;
-  int64_t e0, e1;
-};
-
-__device__ __forceinline__ PostRun post_run(const PostArgs& a) {
-  PostRun r;
-  r.row = (int)(blockIdx.x / (unsigned)a.bpr);
-  r.j = (int)(blockIdx.x - (unsigned)r.row * (unsigned)a.bpr);
-  r.e0 = (int64_t)r.j * a.per_block;
-  r.e1 = r.e0 + a.per_block < a.E ? r.e0 + a.per_block : a.E;
-  return r;
-}
-
-// The lane's trips over its workgroup's run, in element order: f(load(offset)) for U elements per
-// trip, their loads in flight together (four loads per lane: U = 4 of one row, U = 2 of a pair);
-// offset = k*stride + w of element e = k*W + w (the caller adds its row).  An element at or
-// beyond e1 comes as `pad` and is not loaded.
+// The lane's trips over its workgroup's run (tiling.h run_of: a row or pair and the run [lo, hi) of
+// its elements), in element order: f(load(offset)) for U elements per trip, their loads in flight
+// together (four loads per lane: U = 4 of one row, U = 2 of a pair); offset = k*stride + w of
+// element e = k*W + w (tiling.h ElemWalk; the caller adds its row).  An element at or beyond hi
+// comes as `pad` and is not loaded.
 template <int U, class V, class L, class F>
-__device__ __forceinline__ void post_for_each(const PostArgs& a, const PostRun& r, V pad, L load, F f) {
+__device__ __forceinline__ void post_for_each(const PostArgs& a, const Run& r, V pad, L load, F f) {
   // 32-bit lane state: K*W < 2^32, and a run holds at most 2^30 elements (plan_post)
-  const uint32_t W = (uint32_t)a.W, len = (uint32_t)(r.e1 - r.e0);
+  const uint32_t len = (uint32_t)(r.hi - r.lo);
   uint32_t i = threadIdx.x;  // the element's index within the run
   if (i >= len) return;
-  const uint32_t e = (uint32_t)r.e0 + i;
-  uint32_t k = e / W, w = e - k * W;  // once per lane
-  const uint32_t dk = W <= (uint32_t)kBandBlock ? (uint32_t)kBandBlock / W : 0u;  // (uniform) 256 = dk*W + dw
-  const uint32_t dw = (uint32_t)kBandBlock - dk * W, carry = W - dw;               // dw < W
+  ElemWalk at;
+  at.init((uint32_t)r.lo + i, (uint32_t)a.W);
   for (; i < len; i += U * kBandBlock) {
     V v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      v[u] = i + (uint32_t)u * kBandBlock < len ? load((int64_t)k * a.stride + w) : pad;
-      const bool c = w >= carry;  // w + dw >= W, without the sum (W may exceed 2^31)
-      w = c ? w - carry : w + dw;
-      k += dk + (c ? 1u : 0u);
+      v[u] = i + (uint32_t)u * kBandBlock < len ? load((int64_t)at.k * a.stride + at.w) : pad;
+      at.step();
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) f(v[u]);
@@ -113,7 +93,7 @@ __device__ __forceinline__ void post_for_each(const PostArgs& a, const PostRun& 
 }
 
 template <bool LOG>
-__device__ __forceinline__ Mom post_row_moments(const PostArgs& a, const PostRun& run, const double* __restrict__ row) {
+__device__ __forceinline__ Mom post_row_moments(const PostArgs& a, const Run& run, const double* __restrict__ row) {
   Mom m = mom_empty();
   post_for_each<kBandUnroll>(a, run, __builtin_nan(""), [&](int64_t off) { return row[off]; }, [&](double v) {
     const double x = post_g<LOG>(v);
@@ -124,7 +104,7 @@ __device__ __forceinline__ Mom post_row_moments(const PostArgs& a, const PostRun
 
 __device__ __forceinline__ void post_moments(const PostArgs& a) {
   __shared__ Mom s_wave[kBandBlock / 64];
-  const PostRun run = post_run(a);
+  const Run run = run_of(blockIdx.x, a.bpr, a.per_block, a.E);
   const double* row = a.samples + (int64_t)a.rows[run.row] * a.W;
   Mom m = (a.log_mask >> run.row) & 1u ? post_row_moments<true>(a, run, row) : post_row_moments<false>(a, run, row);
   m = block_fold(s_wave, m);
@@ -146,7 +126,7 @@ __device__ __forceinline__ void post_merge(const PostArgs& a) {
 }
 
 template <bool LOG>
-__device__ __forceinline__ void post_row_hist(const PostArgs& a, const PostRun& run, const double* __restrict__ row,
+__device__ __forceinline__ void post_row_hist(const PostArgs& a, const Run& run, const double* __restrict__ row,
                                               uint32_t* s_h, double lo, double wbin, bool flat) {
   const int B = a.n_bins;
   post_for_each<kBandUnroll>(a, run, __builtin_nan(""), [&](int64_t off) { return row[off]; }, [&](double v) {
@@ -157,7 +137,7 @@ __device__ __forceinline__ void post_row_hist(const PostArgs& a, const PostRun& 
 
 __device__ __forceinline__ void post_hist(const PostArgs& a) {
   __shared__ uint32_t s_h[kPostMaxBins];
-  const PostRun run = post_run(a);
+  const Run run = run_of(blockIdx.x, a.bpr, a.per_block, a.E);
   const int t = threadIdx.x, B = a.n_bins;
   const double* cell = a.marg + (int64_t)run.row * kPostMarg;
   if (!(cell[0] > 0.0)) return;  // (uniform) no valid element in this row
@@ -226,7 +206,7 @@ struct PostXY {
 
 // a pair's run: Cov of the jointly valid (x, y), and their 2-D bins when s_h is given
 template <bool LOGX, bool LOGY>
-__device__ __forceinline__ Cov post_pair_run(const PostArgs& a, const PostRun& run, const double* __restrict__ rx,
+__device__ __forceinline__ Cov post_pair_run(const PostArgs& a, const Run& run, const double* __restrict__ rx,
                                              const double* __restrict__ ry, uint32_t* s_h, const double* cx,
                                              const double* cy) {
   const int B = a.n_bins2;
@@ -251,7 +231,13 @@ __device__ __forceinline__ void post_pairs(const PostArgs& a) {
     Cov wave[kBandBlock / 64];  // the fold's cells, once the counts are flushed
   } s;
   uint32_t* const s_h = s.h;
-  const PostRun run = post_run(a);
+  // tiling.h run_of in this kernel's own text: through the call its scalar code is scheduled and
+  // allocated differently
+  Run run;
+  run.row = (int)(blockIdx.x / (unsigned)a.bpr);
+  run.j = (int)(blockIdx.x - (unsigned)run.row * (unsigned)a.bpr);
+  run.lo = (int64_t)run.j * a.per_block;
+  run.hi = run.lo + a.per_block < a.E ? run.lo + a.per_block : a.E;
   const int t = threadIdx.x, p = run.row, B = a.n_bins2;
   const int i = a.pair_i[p], j = a.pair_j[p];
   const bool counts = a.hist2 != nullptr;  // (uniform)

@@ -10,12 +10,9 @@
 // its copy read through a DPP control, and merge(a, b), "a then b".
 #pragma once
 #include "ode_kernels.cuh"
+#include "tiling.h"
 
 namespace oe {
-
-constexpr int kBandBlock = 256;     // threads per workgroup of the passes over a trajectory chunk
-constexpr int kBandUnroll = 4;      // walkers per lane and trip (loads in flight per state)
-constexpr int kBandTile = kBandBlock * kBandUnroll;  // a workgroup's run: a multiple of this
 
 // count, mean and M2 = Σ(x − mean)² of the elements pushed so far
 struct Welford {
@@ -141,23 +138,9 @@ __device__ __forceinline__ Cell merge_partials(Cell r, int n, Part part) {
   return r;
 }
 
-// The tiling of a pass over a trajectory chunk [T][S][W]: workgroup blockIdx.x takes row
-// blockIdx.x div bpr (a grid row or an observation record) and the j-th run of per_block
-// consecutive walkers [w0, w1) (launch_plan.h plan_band_reduce); each wave-instruction reads
-// 512 contiguous bytes of a state row, kBandUnroll of them in flight per state and lane.
-struct WalkerRun {
-  int row, j;
-  int64_t w0, w1;
-};
-
-__device__ __forceinline__ WalkerRun walker_run(int32_t bpr, int64_t per_block, int64_t W) {
-  WalkerRun r;
-  r.row = (int)(blockIdx.x / (unsigned)bpr);
-  r.j = (int)(blockIdx.x - (unsigned)r.row * (unsigned)bpr);
-  r.w0 = (int64_t)r.j * per_block;
-  r.w1 = r.w0 + per_block < W ? r.w0 + per_block : W;
-  return r;
-}
+// The tiling of a pass over a trajectory chunk [T][S][W] is tiling.h's: workgroup blockIdx.x takes
+// run_of(blockIdx.x, bpr, per_block, W), a row (a grid row or an observation record) and a run
+// [lo, hi) of its walkers (launch_plan.h plan_band_reduce), and its lanes walk the run in trips.
 
 // C = Σ_{s∈mask} y_s of kBandUnroll walkers of one lane: w, w + 256, ... below w1 (0.0, not
 // valid, beyond it)
@@ -174,16 +157,16 @@ __device__ __forceinline__ void band_columns(const double* __restrict__ row, int
 }
 
 // the lane's trips over its workgroup's run: f(C, walker) for kBandUnroll walkers per trip, in
-// walker order (a walker at or beyond w1 comes with C = 0.0)
+// walker order (a walker at or beyond the run's end comes with C = 0.0)
 template <class F>
 __device__ __forceinline__ void for_each_walker(const double* __restrict__ row, int64_t W, uint64_t mask,
-                                                const WalkerRun& r, F f) {
-  for (int64_t w = r.w0 + threadIdx.x; w < r.w1; w += kBandTile) {
+                                                const Run& r, F f) {
+  for_each_trip(threadIdx.x, r, [&](int64_t w) {
     double v[kBandUnroll];
-    band_columns(row, W, mask, w, r.w1, v);
+    band_columns(row, W, mask, w, r.hi, v);
 #pragma unroll
-    for (int u = 0; u < kBandUnroll; ++u) f(v[u], w + (int64_t)u * kBandBlock);
-  }
+    for (int u = 0; u < kBandUnroll; ++u) f(v[u], trip_elem(w, u));
+  });
 }
 
 }  // namespace oe

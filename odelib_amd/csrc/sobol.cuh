@@ -14,7 +14,7 @@
 //   k_sobol_accum + k_sobol_merge     a chunk folded into the cells of one block of base rows
 //   k_sobol_finish                    the blocks' cells merged in block order; S1, ST, n_i and
 //                                     n_V, mean, V
-// The accumulate pass is tiled by reduce.cuh's walker runs over the base rows (W := nb), one row
+// The accumulate pass is tiled by tiling.h's runs over the base rows (n := nb), one row
 // and run per workgroup; the columns are the outer loop and the factors go in tiles of
 // kSobolFactorTile, so registers and LDS depend on neither count.  A and B are read once per
 // factor tile, every AB_i once.  Merges run in reduce.cuh's fixed order without floating-point
@@ -27,8 +27,6 @@ namespace oe {
 constexpr int kSobolMaxCols = kBandMaxCols;
 constexpr int kSobolMaxFactors = 32;
 constexpr int kSobolMaxBlocks = 1024;
-constexpr int kSobolVar = 3;   // doubles of the variance cell: n, mean, M2
-constexpr int kSobolCov = 6;   // doubles of a factor cell: n, mx, my, M2x, M2y, Cxy
 constexpr int kSobolIdx = 3;   // k_sobol_finish per (row, column, factor): S1, ST, n_i
 constexpr int kSobolOut = 3;   // k_sobol_finish per (row, column): n_V, mean, V
 // Factors per pass over A and B (1, 2 or 4).  DESIGN.md §3.15 has the alternatives measured on
@@ -37,8 +35,6 @@ constexpr int kSobolOut = 3;   // k_sobol_finish per (row, column): n_V, mean, V
 #define OE_SOBOL_FACTOR_TILE 2
 #endif
 constexpr int kSobolFactorTile = OE_SOBOL_FACTOR_TILE;
-
-__host__ __device__ constexpr int sobol_cell(int d) { return kSobolVar + kSobolCov * d; }
 
 struct SobolArgs {
   const double* values;  // [n_rows][n_states][G·nb]
@@ -109,7 +105,7 @@ template <bool LOG>
 __device__ __forceinline__ void sobol_accum_form(const SobolArgs& a, Welford (&s_var)[kBandBlock / 64],
                                                  Cov (&s_cov)[kBandBlock / 64]) {
   constexpr int PT = kSobolFactorTile;
-  const WalkerRun run = walker_run(a.bpr, a.per_block, a.nb);
+  const Run run = run_of(blockIdx.x, a.bpr, a.per_block, a.nb);
   const int64_t nb = a.nb, Wt = (int64_t)(a.d + 2) * nb;  // doubles between two states of a row
   const double* row = a.values + (int64_t)run.row * a.n_states * Wt;
   const int cell = sobol_cell(a.d);
@@ -121,17 +117,19 @@ __device__ __forceinline__ void sobol_accum_form(const SobolArgs& a, Welford (&s
       Cov cov[PT];
 #pragma unroll
       for (int p = 0; p < PT; ++p) cov[p] = Cov{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int64_t w = run.w0 + threadIdx.x; w < run.w1; w += kBandTile) {
+      // (tiling.h for_each_trip's loop in its own text: as a lambda's body the trip compiles to
+      // other registers and instructions)
+      for (int64_t w = run.lo + threadIdx.x; w < run.hi; w += kBandTile) {
         double va[kBandUnroll], vb[kBandUnroll], vf[PT][kBandUnroll];
-        band_columns(row, Wt, mask, w, run.w1, va);
-        band_columns(row + nb, Wt, mask, w, run.w1, vb);
+        band_columns(row, Wt, mask, w, run.hi, va);
+        band_columns(row + nb, Wt, mask, w, run.hi, vb);
 #pragma unroll
         for (int p = 0; p < PT; ++p)
-          if (p0 + p < a.d) band_columns(row + (int64_t)(2 + p0 + p) * nb, Wt, mask, w, run.w1, vf[p]);
+          if (p0 + p < a.d) band_columns(row + (int64_t)(2 + p0 + p) * nb, Wt, mask, w, run.hi, vf[p]);
 #pragma unroll
         for (int u = 0; u < kBandUnroll; ++u) {
-          // (a base row at or beyond w1 came as 0.0, which the identity form would count)
-          if (w + (int64_t)u * kBandBlock >= run.w1 || !sobol_valid<LOG>(va[u]) || !sobol_valid<LOG>(vb[u])) continue;
+          // (a base row at or beyond hi came as 0.0, which the identity form would count)
+          if (trip_elem(w, u) >= run.hi || !sobol_valid<LOG>(va[u]) || !sobol_valid<LOG>(vb[u])) continue;
           const double fa = sobol_f<LOG>(va[u]), fb = sobol_f<LOG>(vb[u]);
           if (p0 == 0) {
             var.push(fa);

@@ -11,7 +11,7 @@
 //   k_waic_init                     the empty cells (0, 0, 0, −inf, 0)
 //   k_waic_accum + k_waic_merge     a chunk folded into the cells; optionally term stored
 //   k_waic_finish                   the pointwise outputs and their sums, in the caller's order
-// Tiled by reduce.cuh's walker runs, one record and run per workgroup (launch_plan.h plan_waic:
+// Tiled by tiling.h's runs of walkers, one record and run per workgroup (launch_plan.h plan_waic:
 // plan_band_reduce's run).  Merges run in reduce.cuh's fixed order: every output is the same bits
 // run to run for one chunking.
 #pragma once
@@ -19,7 +19,6 @@
 
 namespace oe {
 
-constexpr int kWaicAcc = 5;     // doubles per accumulator cell: n, mean, M2, a, s
 constexpr int kWaicPoint = 6;   // pointwise: n, lppd, p_waic, elpd, mean_ll, max_ll
 constexpr int kWaicSummary = 8; // n_obs_used, lppd, p_waic, elpd_waic, waic, se_elpd, n_high_var, n_rows_min
 constexpr double kWaicHighVar = 0.4;  // p_o above this flags the observation (Vehtari et al. 2017)
@@ -95,7 +94,7 @@ __device__ __forceinline__ void waic_init(double* __restrict__ acc, int64_t n_ce
 
 __device__ __forceinline__ void waic_accum(const WaicArgs& a) {
   __shared__ Lse s_wave[kBandBlock / 64];
-  const WalkerRun run = walker_run(a.bpo, a.per_block, a.W);
+  const Run run = run_of(blockIdx.x, a.bpo, a.per_block, a.W);
   const int o = run.row;
   const cptr<Obs> obs = kconst(a.obs);
   const ObsTerm rec = obs_term(obs + o);
@@ -103,7 +102,7 @@ __device__ __forceinline__ void waic_accum(const WaicArgs& a) {
   double* trow = a.terms ? a.terms + (int64_t)kconst(a.perm)[o] * a.terms_ld + a.w_offset : nullptr;
   Lse c = lse_empty();
   for_each_walker(row, a.W, obs[o].mask, run, [&](double v, int64_t w) {
-    if (w < run.w1) {
+    if (w < run.hi) {
       const double term = chi_term<true>(rec, v);
       const bool valid = __builtin_isfinite(term);
       if (valid) c.push(-term);

@@ -2,25 +2,7 @@
 // plan_band_chunk, plan_band_reduce) on the CPU, under ASan + UBSan (tests/test_band_host.py
 // builds and runs it).  Prints the failing case and exits non-zero; prints one
 // "chunk T S W budget -> value" line per chunk case for the Python restatement's check.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/odelib_amd.h"
-#include "../../odelib_amd/csrc/launch_plan.h"
-
-using namespace oe::plan;
-
-static int g_fail = 0;
-static char g_case[256];
-
-#define CHECK(cond)                                                                \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
-      if (++g_fail > 20) std::exit(1);                                             \
-    }                                                                              \
-  } while (0)
+#include "plan_check.h"
 
 int main() {
   // plan_band_chunk: a multiple of 256, at least 256, never past W rounded up, within the
@@ -67,32 +49,12 @@ int main() {
         std::snprintf(g_case, sizeof g_case, "reduce T=%d W=%lld n_cu=%d", T, (long long)W, n_cu);
         const BandPlan p = plan_band_reduce(T, W, 2, n_cu);
         CHECK(p.block == (unsigned)kBandBlock);
-        CHECK(p.per_block > 0 && p.per_block % kBandTile == 0);
-        CHECK(p.blocks_per_row >= 1);
+        check_runs(p, W);
         CHECK((int64_t)p.grid == (int64_t)T * p.blocks_per_row);
         CHECK(p.partial_bytes == sizeof(double) * 5 * 2 * (size_t)p.grid);
         CHECK((int64_t)p.cell_grid * kBlock >= (int64_t)T * 2);
-        // the kernels' own index arithmetic (band.cuh), counted per walker of every row
-        std::vector<uint8_t> seen((size_t)W);
-        for (int i = 0; i < T; i += (T > 8 ? T - 1 : 1)) {  // first and last row of the tall grids
-          std::fill(seen.begin(), seen.end(), 0);
-          for (unsigned blk = (unsigned)i * p.blocks_per_row; blk < (unsigned)(i + 1) * p.blocks_per_row; ++blk) {
-            const int row = (int)(blk / (unsigned)p.blocks_per_row), j = (int)(blk - (unsigned)row * p.blocks_per_row);
-            CHECK(row == i);
-            const int64_t w0 = (int64_t)j * p.per_block;
-            const int64_t w1 = w0 + p.per_block < W ? w0 + p.per_block : W;
-            CHECK(w0 < W);  // no idle workgroup
-            for (int t = 0; t < kBandBlock; ++t)
-              for (int64_t w = w0 + t; w < w1; w += kBandTile)
-                for (int u = 0; u < kBandTile / kBandBlock; ++u)
-                  if (w + (int64_t)u * kBandBlock < w1) ++seen[(size_t)(w + (int64_t)u * kBandBlock)];
-          }
-          bool once = true;
-          for (int64_t w = 0; w < W; ++w) once = once && seen[(size_t)w] == 1;
-          CHECK(once);
-        }
+        // the kernels' own walk (tiling.h), counted per walker: first and last row of the tall grids
+        for (int i = 0; i < T; i += (T > 8 ? T - 1 : 1)) check_lane_walk(p, i, p.grid, W);
       }
-  if (g_fail) return 1;
-  std::printf("SANITIZE OK\n");
-  return 0;
+  return finish();
 }

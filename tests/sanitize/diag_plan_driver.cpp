@@ -3,25 +3,7 @@
 // and runs it).  The kernels' index arithmetic (diag.cuh) is replayed into host buffers of
 // exactly the planned sizes, so an index past a part is a sanitizer report.  Prints the failing
 // case and exits non-zero; prints "LB <value>" for the Python tests.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/odelib_amd.h"
-#include "../../odelib_amd/csrc/launch_plan.h"
-
-using namespace oe::plan;
-
-static int g_fail = 0;
-static char g_case[256];
-
-#define CHECK(cond)                                                                \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
-      if (++g_fail > 20) std::exit(1);                                             \
-    }                                                                              \
-  } while (0)
+#include "plan_check.h"
 
 int main() {
   std::printf("LB %d\n", kDiagLB);
@@ -102,7 +84,5 @@ int main() {
       for (int t = 1; t <= p.max_lag; ++t) once = once && hit[(size_t)t] == 1;
       CHECK(once);
     }
-  if (g_fail) return 1;
-  std::printf("SANITIZE OK\n");
-  return 0;
+  return finish();
 }

@@ -2,25 +2,7 @@
 // CPU, under ASan + UBSan (tests/test_loo_host.py builds and runs it).  Prints the failing case
 // and exits non-zero.
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "../../include/odelib_amd.h"
-#include "../../odelib_amd/csrc/launch_plan.h"
-
-using namespace oe::plan;
-
-static int g_fail = 0;
-static char g_case[256];
-
-#define CHECK(cond)                                                                \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
-      if (++g_fail > 20) std::exit(1);                                             \
-    }                                                                              \
-  } while (0)
+#include "plan_check.h"
 
 int main() {
   const int64_t Ns[] = {1, 63, 64, 65, 257, 65537, 7400000};
@@ -33,15 +15,16 @@ int main() {
         const LooPlan p = plan_loo(n_obs, n_rows, 1.0, n_cu);
         CHECK(p.error == OE_OK);
         CHECK(p.block == (unsigned)kBandBlock);
-        CHECK(p.per_block > 0 && p.per_block % kBandTile == 0 && p.blocks_per_obs >= 1);
-        CHECK((int64_t)p.grid == (int64_t)n_obs * p.blocks_per_obs);
+        check_runs(p, n_rows);
+        const int bpr = p.blocks_per_row;
+        CHECK((int64_t)p.grid == (int64_t)n_obs * bpr);
         CHECK(p.obs_grid == (unsigned)n_obs);
         CHECK((int64_t)p.cell_grid * kBlock >= n_obs && ((int64_t)p.cell_grid - 1) * kBlock < n_obs);
         // the tiling is k_waic_accum's and depends on (n_obs, n_rows, n_cu) only
         const WaicPlan w = plan_waic(n_obs, n_rows, n_cu);
-        CHECK(p.per_block == w.per_block && p.blocks_per_obs == w.blocks_per_obs);
+        CHECK(p.per_block == w.per_block && bpr == w.blocks_per_row);
         const LooPlan q = plan_loo(n_obs, n_rows, 0.37, n_cu);
-        CHECK(q.error != OE_OK || (q.per_block == p.per_block && q.blocks_per_obs == p.blocks_per_obs));
+        CHECK(q.error != OE_OK || (q.per_block == p.per_block && q.blocks_per_row == bpr));
         // the tail capacity holds M of every N the rows can have, and fits the fit kernel's LDS
         CHECK(p.tail_cap >= 1 && p.tail_cap <= kLooTailMax);
         CHECK(p.tail_cap >= loo_tail_len(n_rows, 1.0));
@@ -57,7 +40,7 @@ int main() {
         CHECK(p.off_acc % 256 == 0 && p.off_tail % 256 == 0 && p.off_c % 256 == 0 && p.bytes % 256 == 0);
         CHECK(p.off_state >= p.off_hist + sizeof(uint32_t) * rows * kLooBins);
         CHECK(p.off_part >= p.off_state + sizeof(uint64_t) * rows * kLooState && p.zero_bytes == p.off_part);
-        CHECK(p.off_acc >= p.off_part + sizeof(double) * rows * (size_t)p.blocks_per_obs * kLooAcc);
+        CHECK(p.off_acc >= p.off_part + sizeof(double) * rows * (size_t)bpr * kLooAcc);
         CHECK(p.off_tail >= p.off_acc + sizeof(double) * rows * kLooAcc);
         CHECK(p.off_c >= p.off_tail + sizeof(double) * rows * (size_t)p.tail_cap);
         CHECK(p.bytes >= p.off_c + sizeof(double) * rows);
@@ -69,29 +52,14 @@ int main() {
         double* acc = reinterpret_cast<double*>(buf.data() + p.off_acc);
         double* tail = reinterpret_cast<double*>(buf.data() + p.off_tail);
         double* c = reinterpret_cast<double*>(buf.data() + p.off_c);
-        std::vector<uint8_t> seen((size_t)n_rows);
         for (int o = 0; o < n_obs; ++o) {
-          const bool walk = o == 0 || o == n_obs - 1 || o == n_obs / 2;  // the lanes of three observations
-          if (walk) std::fill(seen.begin(), seen.end(), 0);
-          for (unsigned blk = (unsigned)o * p.blocks_per_obs; blk < (unsigned)(o + 1) * p.blocks_per_obs; ++blk) {
-            const int rec = (int)(blk / (unsigned)p.blocks_per_obs), j = (int)(blk - (unsigned)rec * p.blocks_per_obs);
-            CHECK(rec == o && blk < p.grid);
-            const int64_t w0 = (int64_t)j * p.per_block;
-            const int64_t w1 = w0 + p.per_block < n_rows ? w0 + p.per_block : n_rows;
-            CHECK(w0 < n_rows);  // no idle workgroup
-            if (walk)
-              for (int t = 0; t < kBandBlock; ++t)
-                for (int64_t w = w0 + t; w < w1; w += kBandTile)
-                  for (int u = 0; u < kBandTile / kBandBlock; ++u) {
-                    const int64_t wu = w + (int64_t)u * kBandBlock;
-                    if (wu < w1) ++seen.at((size_t)wu);
-                  }
-            for (int k = 0; k < kLooAcc; ++k) part[((int64_t)rec * p.blocks_per_obs + j) * kLooAcc + k] += 1.0;
-          }
-          if (walk) {
-            bool once = true;
-            for (int64_t w = 0; w < n_rows; ++w) once = once && seen[(size_t)w] == 1;
-            CHECK(once);
+          // the lanes of three observations, walked as loo.cuh walks them (tiling.h)
+          if (o == 0 || o == n_obs - 1 || o == n_obs / 2) check_lane_walk(p, o, p.grid, n_rows);
+          for (unsigned blk = (unsigned)o * bpr; blk < (unsigned)(o + 1) * bpr; ++blk) {
+            const Run r = run_of(blk, bpr, p.per_block, n_rows);
+            CHECK(r.row == o && blk < p.grid);
+            CHECK(r.lo < n_rows);  // no idle workgroup
+            for (int k = 0; k < kLooAcc; ++k) part[((int64_t)r.row * bpr + r.j) * kLooAcc + k] += 1.0;
           }
           for (int b = 0; b < kLooBins; ++b) hist[(int64_t)o * kLooBins + b] += 1u;
           for (int k = 0; k < kLooState; ++k) st[(int64_t)o * kLooState + k] += 1u;
@@ -101,7 +69,7 @@ int main() {
           c[o] += 1.0;
         }
         bool once = true;
-        for (int64_t k = 0; k < (int64_t)n_obs * p.blocks_per_obs * kLooAcc; ++k) once = once && part[k] == 1.0;
+        for (int64_t k = 0; k < (int64_t)n_obs * bpr * kLooAcc; ++k) once = once && part[k] == 1.0;
         for (int64_t k = 0; k < (int64_t)n_obs * kLooBins; ++k) once = once && hist[k] == 1u;
         for (int64_t k = 0; k < (int64_t)n_obs * kLooState; ++k) once = once && st[k] == 1u;
         for (int64_t k = 0; k < (int64_t)n_obs * kLooAcc; ++k) once = once && acc[k] == 1.0;
@@ -135,7 +103,5 @@ int main() {
     CHECK(loo_tail_len(26, 1.0) == 6 && loo_tail_len(1, 1.0) == 1 && loo_tail_len(0, 1.0) == 0);
     for (int64_t N = 1; N < 200000; N += 1 + N / 50) CHECK(loo_tail_len(N, 1.0) <= loo_tail_len(N + 1, 1.0));
   }
-  if (g_fail) return 1;
-  std::printf("SANITIZE OK\n");
-  return 0;
+  return finish();
 }

@@ -3,42 +3,34 @@
 // kernels' index arithmetic (post.cuh: the runs, the lane's (k, w) walk, the partials) is replayed
 // into host buffers of exactly the planned sizes, so an index past a part is a sanitizer report.
 // Prints the failing case and exits non-zero; prints "WG_PER_CU <value>" for the Python tests.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "plan_check.h"
 
-#include "../../include/odelib_amd.h"
-#include "../../odelib_amd/csrc/launch_plan.h"
-
-using namespace oe::plan;
-
-static int g_fail = 0;
-static char g_case[256];
-
-#define CHECK(cond)                                                                \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
-      if (++g_fail > 20) std::exit(1);                                             \
-    }                                                                              \
-  } while (0)
-
-// the runs of one row: multiples of kBandTile, covering [0, E) exactly once, no idle workgroup,
-// at most 2^30 elements each (the kernels keep a lane's index within its run in 32 bits)
-static void check_runs(const PostPlan& p, int64_t E) {
-  CHECK(p.per_block > 0 && p.per_block % kBandTile == 0);
+// the runs of one row (plan_check.h), at most 2^30 elements each: the kernels keep a lane's index
+// within its run in 32 bits
+static void check_post_runs(const PostPlan& p, int64_t E) {
+  check_runs(p, E);
   CHECK(p.per_block <= (int64_t(1) << 30));
-  CHECK(p.blocks_per_row >= 1);
-  int64_t next = 0;
-  for (int j = 0; j < p.blocks_per_row; ++j) {
-    const int64_t e0 = (int64_t)j * p.per_block;
-    const int64_t e1 = e0 + p.per_block < E ? e0 + p.per_block : E;
-    CHECK(e0 == next);
-    CHECK(e0 < E);  // no idle workgroup
-    CHECK(e1 > e0);
-    next = e1;
-  }
-  CHECK(next == E);
+}
+
+// Lane t's walk over run r of a row [K][W] as post_for_each<U> does it (tiling.h ElemWalk): at every
+// element below the run's end, (k, w) is that element's; seen(k, w) for each.
+template <class F>
+static void walk_elems(const Run& r, int t, int U, int64_t K, int64_t W, F seen) {
+  const uint32_t len = (uint32_t)(r.hi - r.lo);
+  uint32_t i = (uint32_t)t;
+  if (i >= len) return;
+  ElemWalk at;
+  at.init((uint32_t)r.lo + i, (uint32_t)W);
+  CHECK(at.dw < (uint32_t)W);
+  for (; i < len; i += U * kBandBlock)
+    for (int u = 0; u < U; ++u) {
+      if (i + (uint32_t)u * kBandBlock < len) {
+        CHECK((int64_t)at.k * W + at.w == r.lo + i + (int64_t)u * kBandBlock);
+        CHECK(at.k < (uint32_t)K && at.w < (uint32_t)W);
+        seen(at.k, at.w);
+      }
+      at.step();
+    }
 }
 
 int main() {
@@ -53,16 +45,17 @@ int main() {
       for (int n_pairs : prs) {
         std::snprintf(g_case, sizeof g_case, "E=%lld n_sel=%d n_pairs=%d", (long long)E, n_sel, n_pairs);
         const PostPlan p = plan_post(E, n_sel, n_pairs, n_cu);
-        check_runs(p, E);
+        check_post_runs(p, E);
         // a row's runs do not depend on what else is selected
         CHECK(p.per_block == base.per_block && p.blocks_per_row == base.blocks_per_row);
+        const int bpr = p.blocks_per_row;
         CHECK(p.block == (unsigned)kBandBlock);
-        CHECK((int64_t)p.row_grid == (int64_t)n_sel * p.blocks_per_row);
-        CHECK((int64_t)p.pair_grid == (int64_t)n_pairs * p.blocks_per_row);
+        CHECK((int64_t)p.row_grid == (int64_t)n_sel * bpr);
+        CHECK((int64_t)p.pair_grid == (int64_t)n_pairs * bpr);
         // the parts do not overlap and end within the buffer
         const size_t offs[] = {p.off_mpart, p.off_ppart, p.bytes};
-        const size_t need[] = {sizeof(double) * n_sel * (size_t)p.blocks_per_row * kPostMarg,
-                               sizeof(double) * n_pairs * (size_t)p.blocks_per_row * kPostPair};
+        const size_t need[] = {sizeof(double) * n_sel * (size_t)bpr * kPostMarg,
+                               sizeof(double) * n_pairs * (size_t)bpr * kPostPair};
         for (int k = 0; k < 2; ++k) {
           CHECK(offs[k] % 256 == 0);
           CHECK(offs[k] + need[k] <= offs[k + 1]);
@@ -72,21 +65,21 @@ int main() {
         double* mpart = reinterpret_cast<double*>(buf.data() + p.off_mpart);
         double* ppart = reinterpret_cast<double*>(buf.data() + p.off_ppart);
         for (unsigned blk = 0; blk < p.row_grid; ++blk) {
-          const int r = (int)(blk / (unsigned)p.blocks_per_row), j = (int)(blk - (unsigned)r * (unsigned)p.blocks_per_row);
-          CHECK(r < n_sel);
-          for (int k = 0; k < kPostMarg; ++k) mpart[((int64_t)r * p.blocks_per_row + j) * kPostMarg + k] = 1.0;
+          const Run r = run_of(blk, bpr, p.per_block, E);
+          CHECK(r.row < n_sel);
+          for (int k = 0; k < kPostMarg; ++k) mpart[((int64_t)r.row * bpr + r.j) * kPostMarg + k] = 1.0;
         }
         for (unsigned blk = 0; blk < p.pair_grid; ++blk) {
-          const int r = (int)(blk / (unsigned)p.blocks_per_row), j = (int)(blk - (unsigned)r * (unsigned)p.blocks_per_row);
-          CHECK(r < n_pairs);
-          for (int k = 0; k < kPostPair; ++k) ppart[((int64_t)r * p.blocks_per_row + j) * kPostPair + k] = 1.0;
+          const Run r = run_of(blk, bpr, p.per_block, E);
+          CHECK(r.row < n_pairs);
+          for (int k = 0; k < kPostPair; ++k) ppart[((int64_t)r.row * bpr + r.j) * kPostPair + k] = 1.0;
         }
       }
     // the measurement's other workgroup counts, and a small device
     for (int wg : {1, 2, 8, 16, 64})
       for (int cus : {1, 8, 256, 304}) {
         std::snprintf(g_case, sizeof g_case, "E=%lld wg_per_cu=%d n_cu=%d", (long long)E, wg, cus);
-        check_runs(plan_post(E, 3, 3, cus, wg), E);
+        check_post_runs(plan_post(E, 3, 3, cus, wg), E);
       }
   }
 
@@ -100,29 +93,12 @@ int main() {
     const PostPlan p = plan_post(E, 1, 0, 1, 1);  // (few workgroups: several trips per lane)
     std::vector<uint8_t> seen((size_t)(K * stride));
     for (int j = 0; j < p.blocks_per_row; ++j) {
-      const int64_t e0 = (int64_t)j * p.per_block, e1 = e0 + p.per_block < E ? e0 + p.per_block : E;
+      const Run r = run_of((unsigned)j, p.blocks_per_row, p.per_block, E);
       for (int t = 0; t < kBandBlock; ++t)
-        for (int U : {2, 4}) {
-          const uint32_t Wu = (uint32_t)W, len = (uint32_t)(e1 - e0);
-          uint32_t i = (uint32_t)t;
-          if (i >= len) continue;
-          const uint32_t e = (uint32_t)e0 + i;
-          uint32_t k = e / Wu, w = e - k * Wu;
-          const uint32_t dk = Wu <= (uint32_t)kBandBlock ? (uint32_t)kBandBlock / Wu : 0u;
-          const uint32_t dw = (uint32_t)kBandBlock - dk * Wu, carry = Wu - dw;
-          CHECK(dw < Wu);
-          for (; i < len; i += U * kBandBlock)
-            for (int u = 0; u < U; ++u) {
-              if (i + (uint32_t)u * kBandBlock < len) {
-                CHECK((int64_t)k * W + w == e0 + i + (int64_t)u * kBandBlock);
-                CHECK(k < (uint32_t)K && w < Wu);
-                if (U == 4) ++seen[(size_t)((int64_t)k * stride + (int64_t)row * W + w)];
-              }
-              const bool c = w >= carry;
-              w = c ? w - carry : w + dw;
-              k += dk + (c ? 1u : 0u);
-            }
-        }
+        for (int U : {2, 4})
+          walk_elems(r, t, U, K, W, [&](uint32_t k, uint32_t w) {
+            if (U == 4) ++seen[(size_t)((int64_t)k * stride + (int64_t)row * W + w)];
+          });
     }
     bool once = true;
     for (int k = 0; k < K; ++k)
@@ -135,25 +111,9 @@ int main() {
     const int64_t E = (int64_t(1) << 32) - 1;
     std::snprintf(g_case, sizeof g_case, "walk at E=2^32-1 W=%lld", (long long)W);
     const PostPlan p = plan_post(E, 1, 0, n_cu);
-    const int j = p.blocks_per_row - 1;
-    const int64_t e0 = (int64_t)j * p.per_block, e1 = E;
-    const uint32_t Wu = (uint32_t)W, len = (uint32_t)(e1 - e0);
-    for (int t : {0, 255}) {
-      uint32_t i = (uint32_t)t;
-      const uint32_t e = (uint32_t)e0 + i;
-      uint32_t k = e / Wu, w = e - k * Wu;
-      const uint32_t dk = Wu <= (uint32_t)kBandBlock ? (uint32_t)kBandBlock / Wu : 0u;
-      const uint32_t dw = (uint32_t)kBandBlock - dk * Wu, carry = Wu - dw;
-      for (; i < len; i += 4 * kBandBlock)
-        for (int u = 0; u < 4; ++u) {
-          if (i + (uint32_t)u * kBandBlock < len) CHECK((int64_t)k * W + w == e0 + i + (int64_t)u * kBandBlock);
-          const bool c = w >= carry;
-          w = c ? w - carry : w + dw;
-          k += dk + (c ? 1u : 0u);
-        }
-    }
+    const Run r = run_of((unsigned)p.blocks_per_row - 1, p.blocks_per_row, p.per_block, E);
+    CHECK(r.hi == E);
+    for (int t : {0, 255}) walk_elems(r, t, 4, E / W, W, [](uint32_t, uint32_t) {});
   }
-  if (g_fail) return 1;
-  std::printf("SANITIZE OK\n");
-  return 0;
+  return finish();
 }

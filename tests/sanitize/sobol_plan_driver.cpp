@@ -5,44 +5,13 @@
 // an index past a part is a sanitizer report.  Prints the failing case and exits non-zero; prints
 // "chunk T S G budget -> nb" lines for the Python restatement and "WG_PER_CU <value>".
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
+#include "plan_check.h"
 
-#include "../../include/odelib_amd.h"
-#include "../../odelib_amd/csrc/launch_plan.h"
-
-using namespace oe::plan;
-
-static int g_fail = 0;
-static char g_case[256];
-
-#define CHECK(cond)                                                                \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::printf("FAIL %s:%d: %s\n  in %s\n", __FILE__, __LINE__, #cond, g_case); \
-      if (++g_fail > 20) std::exit(1);                                             \
-    }                                                                              \
-  } while (0)
-
-// the runs of one row: multiples of kBandTile but the last, every base row exactly once, no idle
-// workgroup
-static void check_runs(const SobolPlan& p, int n_rows, int64_t nb) {
-  CHECK(p.per_block > 0 && p.per_block % kBandTile == 0);
-  CHECK(p.blocks_per_row >= 1);
+// the runs of one row over its base rows (plan_check.h) and the launch that holds them
+static void check_sobol_runs(const SobolPlan& p, int n_rows, int64_t nb) {
+  check_runs(p, nb);
   CHECK(p.block == (unsigned)kBandBlock);
   CHECK((int64_t)p.grid == (int64_t)n_rows * p.blocks_per_row);
-  int64_t next = 0;
-  for (int j = 0; j < p.blocks_per_row; ++j) {
-    const int64_t w0 = (int64_t)j * p.per_block;
-    const int64_t w1 = w0 + p.per_block < nb ? w0 + p.per_block : nb;
-    CHECK(w0 == next);
-    CHECK(w0 < nb);
-    CHECK(w1 > w0);
-    CHECK(j == p.blocks_per_row - 1 || (w1 - w0) % kBandTile == 0);
-    next = w1;
-  }
-  CHECK(next == nb);
 }
 
 int main() {
@@ -73,12 +42,12 @@ int main() {
         for (int d : {1, 2, 5, 32}) {
           std::snprintf(g_case, sizeof g_case, "runs n_rows=%d nb=%lld d=%d n_cu=%d", n_rows, (long long)nb, d, n_cu);
           const SobolPlan p = plan_sobol(n_rows, nb, 3, d, 4, n_cu);
-          check_runs(p, n_rows, nb);
+          check_sobol_runs(p, n_rows, nb);
           // the runs are plan_band_reduce's over nb for kSobolWgPerCu workgroups per CU in place of
           // 16: they depend on neither d nor the columns
           const BandPlan b = plan_band_reduce(n_rows, nb, 1, std::max(1, n_cu * kSobolWgPerCu / 16));
           CHECK(p.per_block == b.per_block && p.blocks_per_row == b.blocks_per_row);
-          for (int wg : {1, 2, 8, 16, 64}) check_runs(plan_sobol(n_rows, nb, 3, d, 4, n_cu, wg), n_rows, nb);
+          for (int wg : {1, 2, 8, 16, 64}) check_sobol_runs(plan_sobol(n_rows, nb, 3, d, 4, n_cu, wg), n_rows, nb);
         }
 
   // ---- the partials and the cells as the kernels index them, in buffers of the planned bytes
@@ -94,15 +63,15 @@ int main() {
               const SobolPlan p = plan_sobol(n_rows, nb, n_cols, d, n_blocks, n_cu);
               const int cell = sobol_cell(d);
               CHECK(p.cell_bytes == sizeof(double) * (size_t)n_rows * n_cols * cell);
-              CHECK(p.partial_bytes == p.cell_bytes * (size_t)p.blocks_per_row);
+              const int bpr = p.blocks_per_row;
+              CHECK(p.partial_bytes == p.cell_bytes * (size_t)bpr);
               // k_sobol_accum: workgroup (row, j) stores column c's partial
               std::vector<double> part(p.partial_bytes / sizeof(double));
               for (unsigned blk = 0; blk < p.grid; ++blk) {
-                const int row = (int)(blk / (unsigned)p.blocks_per_row);
-                const int j = (int)(blk - (unsigned)row * (unsigned)p.blocks_per_row);
-                CHECK(row < n_rows);
+                const Run r = run_of(blk, bpr, p.per_block, nb);
+                CHECK(r.row < n_rows);
                 for (int c = 0; c < n_cols; ++c) {
-                  double* q = part.data() + (((int64_t)row * p.blocks_per_row + j) * n_cols + c) * cell;
+                  double* q = part.data() + (((int64_t)r.row * bpr + r.j) * n_cols + c) * cell;
                   for (int k = 0; k < cell; ++k) q[k] += 1.0;
                 }
               }
@@ -124,15 +93,15 @@ int main() {
                 const int k = (int)(g - rc * sub);
                 const int off = k == 0 ? 0 : kSobolVar + kSobolCov * (k - 1), len = k == 0 ? kSobolVar : kSobolCov;
                 double* dst = acc.data() + (((int64_t)block * n_rows + i) * n_cols + c) * cell + off;
-                const double* src = part.data() + ((i * p.blocks_per_row) * n_cols + c) * cell + off;
+                const double* src = part.data() + ((i * bpr) * n_cols + c) * cell + off;
                 const int64_t ld = (int64_t)n_cols * cell;
-                for (int j = 0; j < p.blocks_per_row; ++j)
+                for (int j = 0; j < bpr; ++j)
                   for (int e = 0; e < len; ++e) dst[e] += src[j * ld + e];
               }
               const size_t per_block = p.cell_bytes / sizeof(double);
               once = true;
               for (size_t e = 0; e < acc.size(); ++e)
-                once = once && acc[e] == (e / per_block == (size_t)block ? (double)p.blocks_per_row : 0.0);
+                once = once && acc[e] == (e / per_block == (size_t)block ? (double)bpr : 0.0);
               CHECK(once);
             }
 
@@ -146,23 +115,15 @@ int main() {
       std::vector<uint8_t> seen((size_t)n_rows * S * G * nb);
       const int64_t Wt = (int64_t)G * nb;
       for (unsigned blk = 0; blk < p.grid; ++blk) {
-        const int row = (int)(blk / (unsigned)p.blocks_per_row);
-        const int j = (int)(blk - (unsigned)row * (unsigned)p.blocks_per_row);
-        const int64_t w0 = (int64_t)j * p.per_block, w1 = std::min(nb, w0 + p.per_block);
+        const Run r = run_of(blk, p.blocks_per_row, p.per_block, nb);
         for (int g = 0; g < G; ++g)
           for (int s = 0; s < S; ++s)
-            for (int t = 0; t < kBandBlock; ++t)
-              for (int64_t w = w0 + t; w < w1; w += kBandTile)
-                for (int u = 0; u < kBandTile / kBandBlock; ++u)
-                  if (w + (int64_t)u * kBandBlock < w1)
-                    ++seen[(size_t)(((int64_t)row * S + s) * Wt + (int64_t)g * nb + w + (int64_t)u * kBandBlock)];
+            for_each_lane_elem(r, [&](int64_t w) { ++seen[(size_t)(((int64_t)r.row * S + s) * Wt + (int64_t)g * nb + w)]; });
       }
       bool once = true;
       for (uint8_t v : seen) once = once && v == 1;
       CHECK(once);
     }
 
-  if (g_fail) return 1;
-  std::printf("SANITIZE OK\n");
-  return 0;
+  return finish();
 }
